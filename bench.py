@@ -9,11 +9,15 @@ own independent buffers; there is no data-path collective (independent files
 shard one-per-GPU).  torch.distributed is used only for the
 barrier and the max-over-ranks timing.
 
-    python bench.py [--gpus N --steps K --warmup W --workload c1|c2|c3]
+    python bench.py [--gpus N --steps K --warmup W --workload c1|c2|c3] [--full] [--dump-outputs DIR]
 
 Default workload c1 = BASELINE configs[1]: 1x 1 GiB uniform random buffer per
 GPU, default chunk params (64 KiB / 1 MiB / 4 MiB).  Prints ONE JSON line on
-rank 0.
+rank 0.  A plain run sets up, warms up, times the K steps and prints the line;
+--full adds the side legs after the timed region (the scan's roofline, the
+oracle check, CPU baselines, the host path, chunk digests, Encode), none of
+them part of `value`.  --dump-outputs DIR writes the last timed step's cut
+lists as .npy files.
 """
 import argparse
 import ctypes
@@ -631,6 +635,32 @@ def gather_per_rank(dist, world, value, dev):
     return [float(x.item()) for x in out]
 
 
+def dump_outputs(dirname, rank, world, cuts, res=None, cap_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float64
+    .npy files (offsets and lengths are below 2^53, so exact).  cuts.npy: one
+    (buffer, offset, length) row per chunk, buffers in order; res.npy (device
+    workloads): the per-buffer result rows (cuts, bytes consumed, status,
+    cuts needed).  Past `cap_bytes` in all, cuts.npy keeps a fixed seeded sample of
+    its rows, in order.  At N ranks every rank writes its own files
+    (<name>_rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    rows = []
+    for i, c in enumerate(cuts):
+        c = np.asarray(c.cpu().numpy() if hasattr(c, "cpu") else c).astype(np.float64).reshape(-1, 2)
+        rows.append(np.column_stack([np.full(c.shape[0], float(i)), c]))
+    rows = np.concatenate(rows) if rows else np.zeros((0, 3))
+    if res is not None:
+        r = np.asarray(res.cpu().numpy() if hasattr(res, "cpu") else res).astype(np.float64)
+        np.save(os.path.join(dirname, f"res{sfx}.npy"), r)
+        cap_bytes -= r.nbytes
+    keep = max(0, cap_bytes - 4096) // rows[0:1].nbytes if rows.shape[0] else 0
+    if rows.shape[0] > keep:
+        rows = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+    np.save(os.path.join(dirname, f"cuts{sfx}.npy"), rows)
+
+
 def cpu_selftest(args, world, rank):
     """BENCH_CPU_SELFTEST=1: the multi-rank plumbing alone (rendezvous, barrier,
     max-over-ranks time, per-rank gather, the JSON line) over gloo, no GPU.
@@ -689,6 +719,15 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default 200 (device workloads), 5 (host workload c4)")
     ap.add_argument("--warmup", type=int, default=None, help="default 200 (device workloads), 2 (host workload c4)")
     ap.add_argument("--workload", default="c1", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs (the scan's roofline loop and the measured "
+                         "stream-read peak, the per-rank oracle check, CPU baselines, the PCIe-inclusive host "
+                         "path, chunk digests, Encode, the two streams' cut lists compared); without it the run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): cuts.npy, one (buffer, offset, length) row per chunk; device workloads also "
+                         "res.npy, the per-buffer result rows")
     ap.add_argument("--size-mib", type=int, default=0, help="override the per-buffer size (debug)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -726,6 +765,10 @@ def main():
     if args.roofline_only:
         args.digest_reps = args.encode_reps = args.e2e_reps = 0
         args.no_cpu_baseline = True
+    full = args.full or args.roofline_only
+    if not full:  # a plain run: the timed steps and the line, no side leg
+        args.digest_reps = args.encode_reps = args.e2e_reps = 0
+        args.no_cpu_baseline = args.no_parity = True
     host_default = WORKLOADS[args.workload].get("host", False)
     if args.steps is None:
         args.steps = 5 if host_default else 200
@@ -895,23 +938,33 @@ def main():
     per_rank = gather_per_rank(dist, world, t1 - t0, dev)
     value = world * per_rank_bytes * timed_steps / elapsed / GIB if timed_steps else None
 
-    # Roofline pass (after the timed region, not part of `value`): the scan
-    # kernel's duration from hipEvents on its own launch stream, one pass at a
-    # time (no other pass overlapping it), so it is the kernel's own time.
-    L.cdc_profile_collect(None, None, None, None)
-    L.cdc_profile_enable(1)
-    rsteps = args.steps if args.roofline_only else max(5, min(args.steps, 50))
-    for _ in range(rsteps):
+    if args.dump_outputs:
         if host_mode:
-            chunkers.ChunkBuffers(host_bufs, opts)
-        else:
-            batch.launch(streams[0])
-    torch.cuda.synchronize(dev)
-    L.cdc_profile_enable(0)
-    scan_ms, pipe_ms = ctypes.c_double(), ctypes.c_double()
-    launches, scan_bytes = ctypes.c_uint64(), ctypes.c_uint64()
-    _lib.check(L.cdc_profile_collect(ctypes.byref(scan_ms), ctypes.byref(pipe_ms),
-                                     ctypes.byref(launches), ctypes.byref(scan_bytes)), "profile")
+            dump_outputs(args.dump_outputs, rank, world, out)
+        elif step_no[0] == 0:
+            print("bench.py: --dump-outputs needs at least one step", file=sys.stderr)
+            sys.exit(2)
+        else:  # the batch the last step launched
+            dump_outputs(args.dump_outputs, rank, world, *batches[(step_no[0] - 1) % nstreams].results())
+
+    # Roofline pass (--full; after the timed region, not part of `value`): the
+    # scan kernel's duration from hipEvents on its own launch stream, one pass
+    # at a time (no other pass overlapping it), so it is the kernel's own time.
+    if full:
+        L.cdc_profile_collect(None, None, None, None)
+        L.cdc_profile_enable(1)
+        rsteps = args.steps if args.roofline_only else max(5, min(args.steps, 50))
+        for _ in range(rsteps):
+            if host_mode:
+                chunkers.ChunkBuffers(host_bufs, opts)
+            else:
+                batch.launch(streams[0])
+        torch.cuda.synchronize(dev)
+        L.cdc_profile_enable(0)
+        scan_ms, pipe_ms = ctypes.c_double(), ctypes.c_double()
+        launches, scan_bytes = ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(L.cdc_profile_collect(ctypes.byref(scan_ms), ctypes.byref(pipe_ms),
+                                         ctypes.byref(launches), ctypes.byref(scan_bytes)), "profile")
 
     if host_mode:
         host_cuts = out
@@ -919,29 +972,31 @@ def main():
     else:
         cuts, res = batch.results()
         nchunks = int(res[:, 0].sum())
-        for i, other in enumerate(batches[1:], 1):  # every stream's batch produced the same cut lists
+        for i, other in enumerate(batches[1:] if full else (), 1):  # every stream's batch produced the same cut lists
             if step_no[0] <= i:  # never launched (--roofline-only without warmup: only batch 0 runs)
                 continue
             oc, _ = other.results()
             assert all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(cuts, oc)), \
                 "pipelined batches disagree"
 
-    n = max(int(launches.value), 1)
-    scan_avg_ms = scan_ms.value / n
-    pipe_avg_ms = pipe_ms.value / n
-    bytes_per_launch = scan_bytes.value / n
-    achieved = bytes_per_launch / (scan_avg_ms * 1e-3) / 1e9 if scan_avg_ms > 0 else 0.0
-    roofline = dict(bound="hbm", achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 4), traffic=load_traffic(args.workload),
-                    kernel="k_scan (k_scan_f while the MaskL index is fused into it)", kernel_avg_ms=round(scan_avg_ms, 4),
-                    algorithmic_bytes_per_launch=int(bytes_per_launch),
-                    timed_passes=n,
-                    pipeline_avg_ms=round(pipe_avg_ms, 4))
-    if not host_mode:
-        roofline["measured_stream_read"] = stream_read_peak(torch, L, bufs, dev, local)
-        best = roofline["measured_stream_read"].get("best_GBps")
-        if best:
-            roofline["frac_of_measured_peak"] = round(achieved / best, 4)
+    roofline = None
+    if full:
+        n = max(int(launches.value), 1)
+        scan_avg_ms = scan_ms.value / n
+        pipe_avg_ms = pipe_ms.value / n
+        bytes_per_launch = scan_bytes.value / n
+        achieved = bytes_per_launch / (scan_avg_ms * 1e-3) / 1e9 if scan_avg_ms > 0 else 0.0
+        roofline = dict(bound="hbm", achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(achieved / HBM_PEAK_GBS, 4), traffic=load_traffic(args.workload),
+                        kernel="k_scan (k_scan_f while the MaskL index is fused into it)", kernel_avg_ms=round(scan_avg_ms, 4),
+                        algorithmic_bytes_per_launch=int(bytes_per_launch),
+                        timed_passes=n,
+                        pipeline_avg_ms=round(pipe_avg_ms, 4))
+        if not host_mode:
+            roofline["measured_stream_read"] = stream_read_peak(torch, L, bufs, dev, local)
+            best = roofline["measured_stream_read"].get("best_GBps")
+            if best:
+                roofline["frac_of_measured_peak"] = round(achieved / best, 4)
 
     digest = None
     if not host_mode and args.digest_reps > 0:
@@ -1046,7 +1101,7 @@ def main():
             "chunk_digests": digest,
             "encode": encode_res,
         }
-        if host_mode and wl.get("backup") and backup_stats[0]:
+        if full and host_mode and wl.get("backup") and backup_stats[0]:
             bs = backup_stats[0]
             # What bounds the leg is read from its own stage split.  The host's
             # object SHA-256 (objectHasher, snapshot/backup.go:583, 604: one

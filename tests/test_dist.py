@@ -64,6 +64,29 @@ def test_c2_shards_cover_baseline_config():
     assert len(set(seeds)) == 256 and wl["size"] == 64 << 20
 
 
+def test_dump_outputs_rows_and_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: cuts.npy holds one (buffer, offset, length)
+    float64 row per chunk in buffer order, res.npy the result rows; past the
+    byte cap cuts.npy keeps the same seeded sample of rows, in order, on
+    every call."""
+    import numpy as np
+    cuts = [np.array([[0, 70000], [70000, 1 << 32]], np.uint64), np.zeros((0, 2), np.uint64),
+            torch.tensor([[0, 5]], dtype=torch.int64)]
+    res = torch.tensor([[2, 70000 + (1 << 32), 0, 2], [0, 0, 0, 0], [1, 5, 0, 1]], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, cuts, res)
+    got = np.load(tmp_path / "a" / "cuts.npy")
+    assert got.dtype == np.float64
+    assert got.tolist() == [[0, 0, 70000], [0, 70000, float(1 << 32)], [2, 0, 5]]
+    assert np.load(tmp_path / "a" / "res.npy").tolist() == res.double().tolist()
+    many = [np.stack([np.arange(1000), np.arange(1000) + 1], axis=1).astype(np.uint64)]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), 1, 2, many, cap_bytes=4096 + 24 * 100)
+    b, c = (np.load(tmp_path / d / "cuts_rank1.npy") for d in ("b", "c"))
+    assert b.shape == (100, 3) and np.array_equal(b, c)
+    assert (np.diff(b[:, 1]) > 0).all() and np.array_equal(b[:, 2], b[:, 1] + 1)
+    assert not (tmp_path / "b" / "res_rank1.npy").exists()
+
+
 def _run_bench(args, extra_env):
     import json
     import subprocess

@@ -13,10 +13,10 @@ for rep in 1 2; do
   for v in "$@"; do
     lib=""; [ "$v" != base ] && lib="$PWD/plakar_amd/_lib/$v"
     f="$OUT/${v%.so}_cold$rep.json"
-    PLAKAR_CDC_LIB=$lib timeout -k 10 120 python3 bench.py --gpus 1 --steps 20 --warmup 5 $QUIET > "$f" 2> "$f.err"
+    PLAKAR_CDC_LIB=$lib timeout -k 10 120 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 $QUIET > "$f" 2> "$f.err"
     summ "$f" "${v%.so} cold$rep"
     f="$OUT/${v%.so}_warm$rep.json"
-    PLAKAR_CDC_LIB=$lib timeout -k 10 120 python3 bench.py --gpus 1 --steps 200 --warmup 200 $QUIET > "$f" 2> "$f.err"
+    PLAKAR_CDC_LIB=$lib timeout -k 10 120 python3 bench.py --full --gpus 1 --steps 200 --warmup 200 $QUIET > "$f" 2> "$f.err"
     summ "$f" "${v%.so} warm$rep"
   done
 done

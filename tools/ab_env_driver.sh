@@ -9,12 +9,12 @@ summ() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().stri
 for rep in $(seq 1 $REPS); do
   for v in $VALS; do
     f="$OUT/${VAR}_${v}_cold$rep.json"
-    env $VAR=$v timeout -k 10 120 python3 bench.py --gpus 1 --steps 20 --warmup 5 $QUIET > "$f" 2> "$f.err" || exit 1
+    env $VAR=$v timeout -k 10 120 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 $QUIET > "$f" 2> "$f.err" || exit 1
     summ "$f" "$VAR=$v cold$rep"
   done
 done
 for v in $VALS; do
   f="$OUT/${VAR}_${v}_warm.json"
-  env $VAR=$v timeout -k 10 120 python3 bench.py --gpus 1 --steps 200 --warmup 200 $QUIET > "$f" 2> "$f.err" || exit 1
+  env $VAR=$v timeout -k 10 120 python3 bench.py --full --gpus 1 --steps 200 --warmup 200 $QUIET > "$f" 2> "$f.err" || exit 1
   summ "$f" "$VAR=$v warm"
 done

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for rep in 1 2; do
   for t in ${THREADS:-8 16 24 32}; do
     f="$OUT/c4f_t${t}_$rep.json"
-    timeout -k 10 300 python3 bench.py --workload c4f --steps 5 --warmup 1 --no-cpu-baseline --file-threads $t > "$f" 2> "$f.err" || exit 1
+    timeout -k 10 300 python3 bench.py --full --workload c4f --steps 5 --warmup 1 --no-cpu-baseline --file-threads $t > "$f" 2> "$f.err" || exit 1
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(f\"{sys.argv[2]:16s} {d['value']:7.2f} GiB/s  {d['ms_per_step']:.2f} ms/step\")" "$f" "threads=$t rep$rep"
   done
 done

@@ -19,7 +19,7 @@ for v in base "$@"; do
   lib=""; [ "$v" != base ] && lib="$PWD/plakar_amd/_lib/$v"
   for wl in c1 c3; do
     PLAKAR_CDC_LIB=$lib timeout -s KILL 90 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d "$OUT/pmc_${v%.so}_$wl" -o run -- \
-        python3 bench.py --workload $wl --roofline-only --steps 5 --warmup 0 > "$OUT/pmc_${v%.so}_$wl.json" 2> "$OUT/pmc_${v%.so}_$wl.err" || echo "pmc $v $wl failed"
+        python3 bench.py --full --workload $wl --roofline-only --steps 5 --warmup 0 > "$OUT/pmc_${v%.so}_$wl.json" 2> "$OUT/pmc_${v%.so}_$wl.err" || echo "pmc $v $wl failed"
     for k in k_scan k_scan_f; do python tools/pmc_summary.py "$OUT" $k --glob "pmc_${v%.so}_$wl" 2>/dev/null | grep -v "^$" ; done
   done
 done

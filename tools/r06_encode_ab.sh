@@ -14,7 +14,7 @@ for rep in 1 2; do
     for v in base "$V"; do
       lib=""; [ "$v" != base ] && lib="$PWD/plakar_amd/_lib/$v"
       f="$OUT/${wl}_${v%.so}_$rep.json"
-      PLAKAR_CDC_LIB=$lib timeout -k 10 300 python3 bench.py --workload $wl $Q > "$f" 2> "$f.err" || exit 1
+      PLAKAR_CDC_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload $wl $Q > "$f" 2> "$f.err" || exit 1
       python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); e=d['encode']; print(f\"{sys.argv[2]:24s} encode {e['value']:7.1f} GiB/s  {e['ms_per_pass']:.3f} ms/pass\")" "$f" "$wl ${v%.so} $rep"
     done
   done

@@ -14,7 +14,7 @@ for rep in 1 2; do
     for v in base "$V"; do
       lib=""; [ "$v" != base ] && lib="$PWD/plakar_amd/_lib/$v"
       f="$OUT/${wl}_${v%.so}_$rep.json"
-      PLAKAR_CDC_LIB=$lib timeout -k 10 300 python3 bench.py --workload $wl $Q > "$f" 2> "$f.err" || exit 1
+      PLAKAR_CDC_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload $wl $Q > "$f" 2> "$f.err" || exit 1
       python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); h=d['chunk_digests']['hybrid']; p=d['chunk_digests']['pipelined_with_chunking']; print(f\"{sys.argv[2]:24s} hybrid {h['value']:7.1f} GiB/s  {h['ms_per_pass']:.3f} ms  pipelined {p['value']:7.1f}\")" "$f" "$wl ${v%.so} $rep"
     done
   done

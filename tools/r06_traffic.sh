@@ -12,7 +12,7 @@ for wl in c1 c2 c3; do
   k=k_scan; [ $wl = c3 ] && k=k_scan_f
   CDC_MASKL_INDEX=$([ $wl = c3 ] && echo 2 || echo 1) timeout -s KILL 90 rocprofv3 --kernel-trace --pmc FETCH_SIZE \
       --output-format csv -d "$OUT/fetch_$wl" -o run -- \
-      python3 bench.py --workload $wl --roofline-only --steps 5 --warmup 0 > "$OUT/fetch_$wl.json" 2> "$OUT/fetch_$wl.err" || { echo "pmc $wl failed"; exit 1; }
+      python3 bench.py --full --workload $wl --roofline-only --steps 5 --warmup 0 > "$OUT/fetch_$wl.json" 2> "$OUT/fetch_$wl.err" || { echo "pmc $wl failed"; exit 1; }
   echo "== $wl $k"
   python tools/pmc_summary.py "$OUT" $k --glob "fetch_$wl"
 done
