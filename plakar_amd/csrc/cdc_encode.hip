@@ -9,10 +9,10 @@
 //
 // Kernels, in launch order (one batch = the blobs of one call):
 //   k_xxh32       XXH32 of every blob (the frame's content checksum), on a
-//                 side stream: four blobs per wave, a lane quad's chains each
-//   k_lz4_seq     one wave per 16-KiB segment: greedy LZ4 match search, 64
+//                 side stream: one blob per wave, a lane quad's four chains
+//   k_lz4_seq     one wave per 8-KiB segment: greedy LZ4 match search, 64
 //                 positions per step at LZ4's accelerating stride (hash table
-//                 of 4,096 u16 in LDS, matches found by ballot, extended 64
+//                 of 2,048 u16 in LDS, matches found by ballot, extended 64
 //                 bytes per step both ways); sequences out as (match start,
 //                 offset, length) records
 //   k_lz4_size    one workgroup per 4-MiB LZ4 block: literal runs across
@@ -31,8 +31,8 @@
 //                 l, l+64, ... by Horner in H^64 with an 8-bit table, reduced
 //                 once per block, then multiplies by its own H^e), tag
 //
-// Matches stay inside their 16-KiB segment, so compression ratios are those
-// of LZ4 with a 16-KiB window; any LZ4 decoder reads the frames (the tests
+// Matches stay inside their 8-KiB segment, so compression ratios are those
+// of LZ4 with an 8-KiB window; any LZ4 decoder reads the frames (the tests
 // decode them with the system's liblz4).  Nonces and subkeys come from the
 // caller (the host fills them from the OS CSPRNG), as crypto/rand does in
 // the reference; piece k of a blob uses the blob's data nonce with its last
@@ -247,7 +247,7 @@ struct BlobKey {
     G128 t64[256];    // 8-bit table of H^64 (the lanes' Horner steps)
 };
 
-struct Seg {             // a 16-KiB LZ4 search segment
+struct Seg {             // an 8-KiB LZ4 search segment
     uint64_t src;        // byte offset in the input base
     uint32_t len;
     uint32_t rem;        // bytes from the segment's start to its LZ4 block's end
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(kXxWaves * 64) void k_xxh32(const Batch B)
 // match length), segment-relative; the literals before a match are the bytes
 // since the previous match's end.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kSeqWaves = 2;  // 24 KiB of LDS per wave: three workgroups per CU
+constexpr uint32_t kSeqWaves = 2;  // 12 KiB of LDS per wave (the segment and the hash table)
 constexpr uint32_t kSkipShift = 6;  // LZ4's skip trigger
 
 struct alignas(16) SeqLds {

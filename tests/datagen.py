@@ -21,6 +21,15 @@ def low_entropy(n, seed, frac=0.01):
     return out
 
 
+def text_like(n, seed):
+    """Text-like bytes: words drawn uniformly from a small vocabulary (the
+    "text" kind of tests/test_encode.py)."""
+    words = [b"backup ", b"snapshot ", b"chunk ", b"packfile ", b"plakar ", b"%d " % seed]
+    r = np.random.default_rng(seed)
+    s = b"".join(words[j] for j in r.integers(0, len(words), size=n // 4 + 1))
+    return s[:n]
+
+
 def zipf_sizes(count, seed, s=1.1, unit=4096, kmax=32768):
     """C4: file sizes from a bounded Zipf(s) over {unit * k, k = 1..kmax}."""
     k = np.arange(1, kmax + 1, dtype=np.float64)
