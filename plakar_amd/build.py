@@ -28,20 +28,42 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def resources_path(lib=None):
+    """The compiler's per-kernel resource remarks of a built library."""
+    return os.path.splitext(lib or LIB)[0] + ".resources.txt"
+
+
 def build_lib(force=False, verbose=True, out=None, defines=()):
     """Build the library (out: another path for an experiment variant,
-    defines: extra -D flags for it)."""
+    defines: extra -D flags for it).
+
+    The compiler's kernel-resource-usage remarks (registers, spills and
+    private-segment bytes of every kernel) are kept next to the library in
+    resources_path(); tests/test_kernel_resources.py holds k_resolve and
+    k_scan to their private-segment bounds with them."""
     target = out or LIB
-    if not force and not defines and not _stale(target, SOURCES + HEADERS):
+    remarks = resources_path(target)
+    if not force and not defines and not _stale(target, SOURCES + HEADERS) and os.path.exists(remarks):
         return target
     os.makedirs(os.path.dirname(target), exist_ok=True)
     tmp = target + ".tmp"
     cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
            "-I", os.path.join(ROOT, "include"), "-Wall", "-Wno-unused-function",
+           "-Rpass-analysis=kernel-resource-usage",
            "-o", tmp] + [f"-D{d}" for d in defines] + SOURCES
     if verbose:
         print("[plakar_amd.build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
+    # the remarks come on stderr, between any warnings: the remark lines go to
+    # the file, everything else is passed on
+    r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+    kept = [ln for ln in r.stderr.splitlines(True) if "[-Rpass-analysis=kernel-resource-usage]" in ln]
+    sys.stderr.write("".join(ln for ln in r.stderr.splitlines(True)
+                             if "[-Rpass-analysis=kernel-resource-usage]" not in ln))
+    if r.returncode:
+        raise subprocess.CalledProcessError(r.returncode, cmd)
+    with open(remarks + ".tmp", "w") as f:
+        f.writelines(kept)
+    os.replace(remarks + ".tmp", remarks)
     os.replace(tmp, target)
     return target
 

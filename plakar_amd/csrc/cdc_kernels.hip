@@ -1761,8 +1761,17 @@ __device__ __forceinline__ uint32_t row_incl_sum32(uint32_t x)
     return x;
 }
 
-__device__ __noinline__ void lookback(const uint64_t *sg, uint32_t q, uint32_t lane, uint32_t &E, uint64_t &O,
-                                      uint32_t *flags, bool &ab)
+// Returned by value (in registers): E, O and the aborted flag through
+// references put the three of them, and with them every read of E and O on
+// each segment's critical path, in private memory.
+struct LookBack {
+    uint32_t E;
+    uint32_t ab;  // 1: a wait gave up, or a segment below aborted (then E = kSegEnd, O = 0)
+    uint64_t O;
+};
+constexpr LookBack kLookBackAborted = {kSegEnd, 1u, 0ull};
+
+__device__ __noinline__ LookBack lookback(const uint64_t *sg, uint32_t q, uint32_t lane, uint32_t *flags)
 {
     uint32_t Fe = q + lane;  // F, lane t < kJ: entering at hi + 1 + t leaves E = Fe with Fo cuts added
     uint64_t Fo = 0;
@@ -1784,12 +1793,7 @@ __device__ __noinline__ void lookback(const uint64_t *sg, uint32_t q, uint32_t l
             {
                 SpinGuard sp;
                 while (__ballot(valid && !s)) {
-                    if (!sp.ok(flags, kWaitLook, q, uint64_t(lo0))) {
-                        E = kSegEnd;  // gave up: the launch reports CDC_E_DEVICE
-                        O = 0;
-                        ab = true;
-                        return;
-                    }
+                    if (!sp.ok(flags, kWaitLook, q, uint64_t(lo0))) return kLookBackAborted;  // the launch reports CDC_E_DEVICE
                     __builtin_amdgcn_s_sleep(kSpinSleep);
                     if (valid && !s) s = ld_rlx(sg + p);
                 }
@@ -1840,29 +1844,16 @@ __device__ __noinline__ void lookback(const uint64_t *sg, uint32_t q, uint32_t l
             }
             if (istar >= 0) {
                 const uint64_t si = readlane64(s, istar);
-                if ((si >> 62) == 3) {  // aborted below: so is this segment
-                    E = kSegEnd;
-                    O = 0;
-                    ab = true;
-                    return;
-                }
+                if ((si >> 62) == 3) return kLookBackAborted;  // aborted below: so is this segment
                 const uint32_t ep = uint32_t((si >> 38) & 0xFFFFFFu);
                 const uint64_t op = si & ((1ull << 38) - 1);
-                if (ep == kSegEnd) {
-                    E = kSegEnd;
-                    O = op;
-                    return;
-                }
+                if (ep == kSegEnd) return LookBack{kSegEnd, 0u, op};
                 const int64_t t = int64_t(ep) - lo;
                 if (slow || t >= 64 + int64_t(kJ)) goto slow_path;
-                if (t >= 64) {  // passes this window: enters F directly
-                    E = uint32_t(__builtin_amdgcn_readlane(int(Fe), int(t - 64)));
-                    O = op + readlane64(Fo, int(t - 64));
-                } else {
-                    E = uint32_t(__builtin_amdgcn_readlane(int(ce), int(t)));
-                    O = op + readlane64(co, int(t));
-                }
-                return;
+                if (t >= 64)  // passes this window: enters F directly
+                    return LookBack{uint32_t(__builtin_amdgcn_readlane(int(Fe), int(t - 64))), 0u,
+                                    op + readlane64(Fo, int(t - 64))};
+                return LookBack{uint32_t(__builtin_amdgcn_readlane(int(ce), int(t))), 0u, op + readlane64(co, int(t))};
             }
             Fe = ce;
             Fo = co;
@@ -1872,22 +1863,11 @@ slow_path:  // q - 1's own INCLUSIVE status
     uint64_t sq;
     SpinGuard sp;
     while (((sq = readlane64(ld_rlx(sg + q - 1), 0)) >> 62) < 2) {
-        if (!sp.ok(flags, kWaitLookSlow, q, 0)) {
-            E = kSegEnd;
-            O = 0;
-            ab = true;
-            return;
-        }
+        if (!sp.ok(flags, kWaitLookSlow, q, 0)) return kLookBackAborted;
         __builtin_amdgcn_s_sleep(kSpinSleep);
     }
-    if ((sq >> 62) == 3) {
-        E = kSegEnd;
-        O = 0;
-        ab = true;
-        return;
-    }
-    E = uint32_t((sq >> 38) & 0xFFFFFFu);
-    O = sq & ((1ull << 38) - 1);
+    if ((sq >> 62) == 3) return kLookBackAborted;
+    return LookBack{uint32_t((sq >> 38) & 0xFFFFFFu), 0u, sq & ((1ull << 38) - 1)};
 }
 
 // A result row's status, settled once: the scan kernel marks every row
@@ -1901,7 +1881,10 @@ __device__ __forceinline__ void settle_row(cdc_result *res, int64_t st)
                                          __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __noinline__ void abort_rows(const Batch &B, uint32_t lane)
+// Inlined: called out of line it takes the address of B, and the compiler then
+// keeps a copy of the whole by-value kernel argument in every lane's private
+// memory.
+__device__ __forceinline__ void abort_rows(const Batch &B, uint32_t lane)
 {
     for (uint32_t i = lane; i < B.nbufs; i += 64)
         __hip_atomic_store(&B.b[i].res->status, int64_t(CDC_E_DEVICE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2141,7 +2124,10 @@ __device__ __forceinline__ void resolve_segment(const Batch &B, const DevParams 
     uint64_t O = 0;
     if (q > 0 && !aborted) {
         if (l0) st_rlx(W.sg + g, kKindLocal | (uint64_t(conv == kConvEnd ? kConvEnd : conv - q) << 40) | cuts);
-        lookback(sgb, q, lane, E, O, W.flags, aborted);
+        const LookBack lb = lookback(sgb, q, lane, W.flags);
+        E = lb.E;
+        O = lb.O;
+        aborted = lb.ab != 0;
     }
     if (l0) dbg_ts(B, kTsRes + 8 * g + 3);
     const bool on = E == q && !aborted;
@@ -2242,7 +2228,15 @@ __global__ CDC_RESOLVE_ATTR __launch_bounds__(kWalkWavesPerWG * 64) void k_resol
     __shared__ uint64_t s_grec[kWalkWavesPerWG][kGRecs];
     __shared__ uint64_t s_gx[kWalkWavesPerWG][kGExtra];
     __shared__ uint32_t s_ticket;
+    // wave stays a VGPR expression: through readfirstlane the segment number is
+    // uniform and the BufDesc fields become scalar loads from the kernarg
+    // segment instead of three vector loads, but k_resolve then measured the
+    // same on C1 and 2 us slower on C3 (p2s in profiles/pr3_resolve_ab_traces.txt).
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    // One ticket per workgroup.  A ticket per wave (wave_ticket), with the
+    // barrier moved behind the segment's record loads, was measured and lost:
+    // the waves' starts spread over 8 us instead of 3, with 1,024 atomics on
+    // one word instead of 256 (profiles/pr3_resolve_phases.txt).
     if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(W.tick, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     fill_gear_lds<kWalkWavesPerWG * 64, kWCopies>(s_tab, W.gear);
     __syncthreads();

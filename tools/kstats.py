@@ -1,5 +1,5 @@
 """Summarise a rocprofv3 rocpd database (or kernel_trace CSV) per kernel:
-calls, total/avg/min/max duration (us).  Usage: python tools_kstats.py <db|csv>"""
+calls, total/avg/min/max duration (us).  Usage: python tools/kstats.py <db|csv> [--last N] [--seq]"""
 import csv
 import sqlite3
 import sys
@@ -17,12 +17,14 @@ def rows(path):
                 yield r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])
 
 
-def main(path):
+def main(path, last=0):
     d = defaultdict(list)
     seq = list(rows(path))
     for name, s, e in seq:
         short = name.split("(")[0].replace("void ", "")
         d[short].append((e - s) / 1000.0)
+    if last:  # only each kernel's last `last` calls (drops a bench run's warm-up launches)
+        d = {k: v[-last:] for k, v in d.items()}
     tot = sum(sum(v) for v in d.values())
     print(f"{'kernel':48s} {'calls':>6s} {'total_us':>10s} {'avg_us':>9s} {'min_us':>9s} {'max_us':>9s} {'pct':>6s}")
     for k, v in sorted(d.items(), key=lambda kv: -sum(kv[1])):
@@ -32,7 +34,7 @@ def main(path):
 
 
 if __name__ == "__main__":
-    seq = main(sys.argv[1])
+    seq = main(sys.argv[1], int(sys.argv[sys.argv.index("--last") + 1]) if "--last" in sys.argv else 0)
     if "--seq" in sys.argv:
         base = seq[0][1]
         for name, s, e in seq[-14:]:
