@@ -169,6 +169,56 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
 /* Upper bound of one blob's encoding (for out_cap). */
 uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
 
+/* ---- Decode: open the AES-256-GCM stream, then inflate the LZ4 frame -----------
+ * (*Repository).Decode (repository/repository.go:186-210) of n encoded blobs
+ * that sit in device memory at d_in + offsets[i], lens[i] bytes each:
+ *   key != NULL (32 bytes, host memory): encryption.DecryptStream
+ *     (encryption/symmetric.go:165-243): the subkey is opened from the first
+ *     60 bytes, then every record nonce (12) || ciphertext (<= 65536) || tag
+ *     (16) with the nonce it carries; record boundaries follow from the
+ *     length, min(remaining, 65580) bytes each.  A blob under 60 bytes or a
+ *     trailing record under 28 is CDC_E_CORRUPT (the reference takes exactly
+ *     12 trailing bytes for a clean end; no writer produces them and they are
+ *     rejected here), a tag that does not verify CDC_E_AUTH.
+ *   compressed != 0: compression.InflateLZ4Stream (compression/compression.go:
+ *     148-160; empty input is an empty blob, compression.go:108-116): one LZ4
+ *     frame of independent blocks, any block maximum, with or without block
+ *     checksums, content size and content checksum, all verified
+ *     (CDC_E_CORRUPT).  Linked blocks, a dictionary ID, skippable and legacy
+ *     frames are CDC_E_UNSUPPORTED (pierrec/lz4 v4's writer makes none).
+ *   compressed == 0 and key == NULL: a plain copy.
+ * Blob i's plaintext lands at d_out + out_offsets[i] (host array of n + 1,
+ * out_offsets[n] = total), blobs packed without padding, so (out_offsets[i],
+ * out_offsets[i + 1] - out_offsets[i]) is a cdc_cut for the digest entry
+ * points.  Returns CDC_OK whenever the batch ran: status[i] (host, n) is
+ * CDC_OK or blob i's error, and a failed blob contributes 0 bytes.  Decoded
+ * sizes are not stored in the blobs, so the call sizes them on the device
+ * first: when they exceed out_cap it returns CDC_E_NOSPACE with
+ * out_offsets[n] the capacity needed and nothing written (d_out may be NULL
+ * when out_cap is 0).  d_out[out_offsets[n], out_cap) is scratch for the
+ * call: a frame whose content checksum fails is found out only after it was
+ * written, the blobs after it are then moved down over it, and the bytes
+ * between the final out_offsets[n] and the total planned before that failure
+ * are left overwritten.  Keep nothing of your own behind out_offsets[n] in
+ * the same buffer.  Synchronous on `stream`. */
+#define CDC_E_AUTH     (-12) /* a GCM tag did not verify (sealed subkey or a data record) */
+#define CDC_E_CORRUPT  (-13) /* malformed stream: short record, bad LZ4 frame/block, checksum or content-size mismatch */
+#define CDC_E_MISMATCH (-14) /* cdc_check_device: decoded fine, SHA-256 differs from the expected checksum */
+int cdc_decode_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                      int compressed, const uint8_t *key, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
+                      int32_t *status, void *stream);
+
+/* The blob check of snapshot/check.go:83-98 (decode, hash, compare with the
+ * index checksum) without the plaintext leaving the device: decodes into
+ * d_scratch as cdc_decode_device does (CDC_E_NOSPACE and *needed, when given,
+ * the capacity to retry with), hashes every blob that decoded with the
+ * SHA-256 kernels of cdc_chunk_digests_device_async (so cdc_init must have
+ * run) and compares with checksums (host, 32 bytes per blob) on the device.
+ * status[i]: CDC_OK, CDC_E_MISMATCH, or blob i's decode error. */
+int cdc_check_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                     int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_scratch,
+                     uint64_t scratch_cap, uint64_t *needed, int32_t *status, void *stream);
+
 /* ---- packfile builder: the consumer of the cut lists ---------------------------
  * snapshot/packer.go + packfile/packfile.go: blobs are appended to a
  * packfile whose bytes are those of (*PackFile).Serialize (packfile.go:241-294):

@@ -8,7 +8,9 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
     plakar_amd.chunkers    ChunkerOpts / NewChunker / Chunker.Next / ChunkBuffers
     plakar_amd.repository  Repository.Chunker / chunkify routing
     plakar_amd.device      device-resident batches (torch tensors in HBM)
+    plakar_amd.encode      Repository.Encode on the device (DeviceEncoder)
+    plakar_amd.decode      Repository.Decode and the blob check on the device (DeviceDecoder)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "build"]

@@ -28,6 +28,9 @@ CDC_E_MAX_SIZE = -8
 CDC_E_IO = -9
 CDC_E_NOT_INIT = -10
 CDC_E_NO_DEVICE = -11
+CDC_E_AUTH = -12
+CDC_E_CORRUPT = -13
+CDC_E_MISMATCH = -14
 
 
 class cdc_opts(ctypes.Structure):
@@ -173,6 +176,13 @@ SIGNATURES = {
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                          ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
     "cdc_encode_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int]),
+    "cdc_decode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
+                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
+                                         ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_void_p]),
+    "cdc_check_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
+                                        ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
+                                        ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32),
+                                        ctypes.c_void_p]),
     "cdc_set_debug_mode": (ctypes.c_int, [ctypes.c_int]),
     "cdc_gear_is_placeholder": (ctypes.c_int, []),
     "cdc_set_maskl_index_mode": (ctypes.c_int, [ctypes.c_int]),

@@ -778,6 +778,9 @@ const char *cdc_strerror(int s)
     case CDC_E_IO: return "reader error";
     case CDC_E_NOT_INIT: return "cdc_init() has not been called";
     case CDC_E_NO_DEVICE: return "no HIP device available";
+    case CDC_E_AUTH: return "a GCM tag did not verify";
+    case CDC_E_CORRUPT: return "malformed encoded stream";
+    case CDC_E_MISMATCH: return "decoded blob does not match its checksum";
     default: return "unknown status";
     }
 }

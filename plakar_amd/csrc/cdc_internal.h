@@ -212,3 +212,9 @@ int packer_seal(cdc_packer *p, int64_t timestamp, const uint8_t **data, uint64_t
 void packer_reserve(cdc_packer *p, uint64_t max_blob);
 
 }  // namespace cdc
+
+// cdc_encode.hip: the AES tables (Te0 and the S-box), built on the host; each
+// .hip file that needs them uploads its own __device__ copies.
+namespace enc {
+void build_tables(uint32_t te0[256], uint8_t sbox[256]);
+}

@@ -1,0 +1,156 @@
+"""Decode on the device: plakar's (*Repository).Decode (repository/repository.go:
+186-210) for a batch of blobs -- encryption.DecryptStream (encryption/
+symmetric.go:165-243) when a key is configured, then compression.
+InflateLZ4Stream (compression/compression.go:148-160) -- and the blob check of
+snapshot/check.go:83-98 (decode, SHA-256, compare) with the plaintext staying
+on the device.  Every call goes through the C ABI (cdc_decode_device,
+cdc_check_device)."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import CdcError, check, ensure_init, lib
+
+
+class DecodeError(CdcError):
+    """One blob's failure: CDC_E_AUTH, CDC_E_CORRUPT or CDC_E_UNSUPPORTED in .status."""
+
+
+def _key(key):
+    if key is None:
+        return None
+    key = bytes(key)
+    if len(key) != 32:
+        raise ValueError("the repository key is 32 bytes (AES-256)")
+    return key
+
+
+def _u64(a, n):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1))
+    if a.size != n:
+        raise ValueError("offsets and lens differ in length")
+    return a
+
+
+def _ptr(a, ctype):
+    return a.ctypes.data_as(ctypes.POINTER(ctype)) if a.size else (ctype * 1)()
+
+
+def decode_device(base, offsets, lens, out, key=None, compressed=True, device=0, stream=None):
+    """Decode the encoded blobs that live in the device tensor `base` (uint8)
+    at the given byte offsets/lengths into the device tensor `out`: returns
+    (out_offsets, status), n + 1 int64 offsets and n int32 codes.  Blob i's
+    plaintext is out[out_offsets[i]:out_offsets[i + 1]]; a failed blob has
+    status[i] != 0 and no bytes.  Raises CdcError(CDC_E_NOSPACE) when `out` is
+    too small (.needed: the bytes to retry with)."""
+    import torch
+    ensure_init()
+    n = len(lens)
+    offs_a, lens_a = _u64(offsets, n), _u64(lens, n)
+    oo_a = np.zeros(n + 1, dtype=np.uint64)
+    st_a = np.zeros(n, dtype=np.int32)
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    rc = lib().cdc_decode_device(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs_a, ctypes.c_uint64),
+                                 _ptr(lens_a, ctypes.c_uint64), n, int(bool(compressed)), _key(key),
+                                 ctypes.c_void_p(out.data_ptr()), out.numel(), _ptr(oo_a, ctypes.c_uint64),
+                                 _ptr(st_a, ctypes.c_int32), ctypes.c_void_p(s.cuda_stream))
+    if rc < 0:
+        err = CdcError(rc, "cdc_decode_device")
+        err.needed = int(oo_a[n]) if rc == _lib.CDC_E_NOSPACE else None
+        raise err
+    return oo_a.astype(np.int64), st_a
+
+
+def _upload(blobs, device):
+    import torch
+    arrs = [np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview))
+            else np.asarray(b, np.uint8).ravel() for b in blobs]
+    lens = np.array([a.size for a in arrs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    base = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, device=torch.device("cuda", device))
+    if int(offs[-1]):
+        base[:int(offs[-1])].copy_(torch.from_numpy(np.concatenate(arrs)))
+    return base, offs[:-1], lens
+
+
+def decode_blobs(blobs, key=None, compressed=True, device=0):
+    """Decode host byte buffers: a list with each blob's plaintext (bytes), or
+    a DecodeError in the place of a blob that did not decode."""
+    import torch
+    if not len(blobs):
+        return []
+    base, offs, lens = _upload(blobs, device)
+    # decoded sizes are not stored in the blobs: a first guess, then the size the call reports
+    cap = max(int(lens.sum()) * (4 if compressed else 1), 1 << 16)
+    while True:
+        out = torch.empty(cap, dtype=torch.uint8, device=base.device)
+        try:
+            oo, st = decode_device(base, offs, lens, out, key=key, compressed=compressed, device=device)
+            break
+        except CdcError as e:
+            if e.status != _lib.CDC_E_NOSPACE or e.needed <= cap:
+                raise
+            cap = e.needed
+    host = out[:int(oo[-1])].cpu().numpy()
+    return [DecodeError(int(st[i]), f"blob {i}") if st[i] else host[oo[i]:oo[i + 1]].tobytes()
+            for i in range(len(blobs))]
+
+
+def check_blobs(blobs, checksums, key=None, compressed=True, device=0):
+    """snapshot/check.go:83-98 for a batch: decode each blob, hash it and
+    compare with its 32-byte checksum, all on the device.  Returns the int32
+    status array: 0, CDC_E_MISMATCH, or the blob's decode error."""
+    import torch
+    n = len(blobs)
+    if len(checksums) != n:
+        raise ValueError("one checksum per blob")
+    if n == 0:
+        return np.zeros(0, dtype=np.int32)
+    want = b"".join(bytes(c) for c in checksums)
+    if len(want) != 32 * n:
+        raise ValueError("a checksum is 32 bytes (SHA-256)")
+    ensure_init()
+    base, offs, lens = _upload(blobs, device)
+    st_a = np.zeros(n, dtype=np.int32)
+    needed = ctypes.c_uint64()
+    s = torch.cuda.current_stream(device)
+    cap = max(int(lens.sum()) * (4 if compressed else 1), 1 << 16)
+    while True:
+        scratch = torch.empty(cap, dtype=torch.uint8, device=base.device)
+        rc = lib().cdc_check_device(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs, ctypes.c_uint64),
+                                    _ptr(lens, ctypes.c_uint64), n, int(bool(compressed)), _key(key), want,
+                                    ctypes.c_void_p(scratch.data_ptr()), cap, ctypes.byref(needed),
+                                    _ptr(st_a, ctypes.c_int32), ctypes.c_void_p(s.cuda_stream))
+        if rc == _lib.CDC_E_NOSPACE and needed.value > cap:
+            cap = needed.value
+            continue
+        check(rc, "cdc_check_device")
+        return st_a
+
+
+class DeviceDecoder:
+    """(*Repository).Decode with the repository's configuration, the
+    counterpart of DeviceEncoder: compression "LZ4" or None, and the
+    encryption key (None: not encrypted).  `decode_many` decodes a batch in
+    one device call, `check_many` verifies a batch against its checksums;
+    calling the object decodes one blob, like Decode (and raises its error)."""
+
+    def __init__(self, key=None, compression="LZ4", device=0):
+        if compression not in (None, "LZ4"):
+            raise ValueError(f"unsupported compression {compression!r} (the device path implements LZ4)")
+        self.key = _key(key)
+        self.compressed = compression == "LZ4"
+        self.device = device
+
+    def decode_many(self, blobs):
+        return decode_blobs(blobs, key=self.key, compressed=self.compressed, device=self.device)
+
+    def check_many(self, blobs, checksums):
+        return check_blobs(blobs, checksums, key=self.key, compressed=self.compressed, device=self.device)
+
+    def __call__(self, blob):
+        r = self.decode_many([blob])[0]
+        if isinstance(r, DecodeError):
+            raise r
+        return r
