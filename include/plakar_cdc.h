@@ -363,6 +363,136 @@ void cdc_backup_free(cdc_backup *b);
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
                    cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats);
 
+/* ---- restore: packfiles in, files out --------------------------------------------
+ * The read path of snapshot/restore.go:103-110 (a reader per file handed to
+ * the exporter), snapshot/vfs/vfilep.go:58-122 (Read walks the chunk lengths,
+ * one GetBlob per chunk) and repository/repository.go:407-429, 449-466
+ * (GetSubpartForBlob, one ranged packfile read and one Decode per chunk), as
+ * a pipeline over batches that decodes every distinct blob of a batch once. */
+#define CDC_E_NOTFOUND (-15) /* a chunk's checksum is in no registered packfile (repository.ErrPackfileNotFound) */
+
+/* packfile.NewFromBytes (packfile/packfile.go:152-239) for the plain
+ * Serialize form (packfile.go:241-294; the form cdc_packer_serialize and
+ * cdc_backup_files' on_pack produce): the footer, and the index rows into
+ * rows[0, cap) (rows may be NULL when cap is 0).  With cap < count it returns
+ * CDC_E_NOSPACE, *needed (may be NULL) = count, and the footer and the first
+ * cap rows are set.  CDC_E_CORRUPT: fewer than 52 bytes, a version other than
+ * 100, an index that is not 41 * count bytes, an entry whose offset + length
+ * passes the index offset, or an index whose SHA-256 (cdc_sha256) is not the
+ * footer's.  Host only; needs no cdc_init.  The PutPackfile form, whose index
+ * and footer went through Encode (snapshot/snapshot.go:249-267), is not read. */
+typedef struct cdc_packfile_footer {
+    uint32_t version;       /* 100 */
+    uint32_t count;
+    int64_t timestamp;
+    uint32_t index_offset;  /* = the length of the blob data */
+    uint32_t reserved;
+    uint8_t index_checksum[32];
+} cdc_packfile_footer;
+typedef struct cdc_packfile_row {
+    uint8_t checksum[32];
+    uint32_t offset, length;  /* of the encoded blob in the packfile */
+    uint8_t type;             /* 1: TYPE_CHUNK */
+    uint8_t reserved[3];
+} cdc_packfile_row;
+int cdc_packfile_index(const uint8_t *bytes, uint64_t len, cdc_packfile_footer *footer, cdc_packfile_row *rows,
+                       uint64_t cap, uint64_t *needed);
+
+/* The copy loop of vfilep.go:58-122 (`copy(p, data[...])` per chunk) for a
+ * batch, on the device: for each of n segments (host arrays), d_dst[dst_off[i],
+ * + len[i]) = d_src[src_off[i], + len[i]).  Any byte alignment on either
+ * side; sources may repeat and overlap each other (a deduplicated chunk);
+ * destinations are sorted by dst_off and disjoint, and [d_src, + src_cap) and
+ * [d_dst, + dst_cap) do not overlap.  Exactly the bytes asked for are written.
+ * Checked on the host before anything is launched (CDC_E_INVALID): NULL
+ * arrays, src_off + len > src_cap, dst_off + len > dst_cap, destinations
+ * unsorted or overlapping.  The segment arrays are copied before the call
+ * returns.  Asynchronous on `stream`. */
+int cdc_assemble_device(int device, const void *d_src, uint64_t src_cap, const uint64_t *src_off,
+                        const uint64_t *len, const uint64_t *dst_off, uint64_t n, void *d_dst, uint64_t dst_cap,
+                        void *stream);
+/* Cache policy of the assemble kernel: bit 0 nontemporal loads, bit 1
+ * nontemporal stores (default 2).  The bytes written never
+ * depend on it.  Diagnostic, not a reference interface.  CDC_OK or CDC_E_INVALID. */
+int cdc_debug_set_assemble_policy(int policy);
+
+/* A restore context: Decode's configuration (compress, key: as
+ * cdc_decode_device; the key is copied), the registered packfiles with their
+ * locator (checksum -> packfile, offset, length: state.GetSubpartForBlob,
+ * repository.go:449-466), three streams and its pinned / device buffers kept
+ * across runs (grown on demand).  One cdc_restore_files at a time per context. */
+typedef struct cdc_restore_opts {
+    int compress;
+    const uint8_t *key;    /* 32-byte repository key, or NULL: not encrypted */
+    int verify;            /* 0: off; otherwise every decoded blob's SHA-256 is compared with its checksum */
+    int writers;          /* reader and writer threads (0: 8) */
+    uint64_t batch_bytes;  /* output bytes per batch (0: 256 MiB) */
+} cdc_restore_opts;
+/* verify = 1, everything else 0. */
+void cdc_restore_default_opts(cdc_restore_opts *out);
+typedef struct cdc_restore_file {
+    const char *path;          /* destination, or NULL: on_file receives the bytes */
+    uint64_t nchunks;
+    const uint8_t *checksums;  /* 32 B per chunk (Chunk.Checksum) */
+    const uint32_t *lengths;   /* Chunk.Length */
+} cdc_restore_file;
+typedef struct cdc_restore_result {
+    int index;                 /* position in files */
+    int status;                /* CDC_OK, CDC_E_NOTFOUND, CDC_E_IO, CDC_E_MISMATCH or the blob's Decode error */
+    uint64_t size;             /* the file's size (sum of its chunk lengths) */
+    uint32_t piece, pieces;    /* path == NULL: this call's piece of the file (pieces == 1: all of it) */
+    const uint8_t *data;       /* path == NULL and status == CDC_OK: file bytes [data_offset, + data_len) */
+    uint64_t data_offset, data_len;
+} cdc_restore_result;
+typedef struct cdc_restore_stats {
+    uint64_t files, failed_files, bytes, segments;  /* bytes: output bytes of the batches */
+    uint64_t distinct_blobs;   /* distinct checksums among the chunks of the files that were found */
+    uint64_t decoded_blobs, encoded_bytes, decoded_bytes;  /* through Decode: each batch's distinct blobs, summed */
+    uint64_t batches, batches_identity;  /* identity: decoded straight into the output image, no assemble launch */
+    uint64_t pieces;
+    double read_s, h2d_s, decode_s, verify_s, assemble_s, d2h_s, write_s;  /* wall time of each stage, summed */
+    double wall_s;
+} cdc_restore_stats;
+typedef void (*cdc_restore_file_fn)(void *ctx, const cdc_restore_result *r);
+typedef struct cdc_restore cdc_restore;
+int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out);
+/* Parse the index (cdc_packfile_index) and enter every TYPE_CHUNK row into the
+ * locator; a checksum already there keeps its first location.  The memory
+ * form reads the blobs from `bytes` during later runs: the buffer must stay
+ * valid and unchanged until cdc_restore_free (from cgo: C or pinned memory,
+ * never a Go pointer).  The path form reads the footer and the index now and
+ * pread(2)s blob ranges during a run (the fs backend's GetPackfileBlob).
+ * CDC_E_CORRUPT, CDC_E_IO (the path form), CDC_E_NOMEM. */
+int cdc_restore_add_packfile(cdc_restore *r, const uint8_t *bytes, uint64_t len);
+int cdc_restore_add_packfile_path(cdc_restore *r, const char *path);
+/* Restore n files from their chunk lists (what cdc_backup_files' on_file
+ * delivered: Object.Chunks).  Per batch of at most batch_bytes of output (a
+ * larger file goes in pieces cut on chunk boundaries): reader threads gather
+ * the batch's distinct encoded blobs into a pinned arena, one host-to-device
+ * copy, one Decode over the distinct blobs (with verify: plus SHA-256 and
+ * compare, as cdc_check_device), cdc_assemble_device into the batch's output
+ * image (skipped when the plaintext buffer already is that image), one
+ * device-to-host copy, then writer threads pwrite(2) each file's bytes.
+ * Batch k + 1's reads and upload overlap batch k's device stages and batch
+ * k - 1's download and writes.
+ * Failures are per file and the run goes on (FileErrorEvent, restore.go:
+ * 103-116): CDC_E_NOTFOUND for a checksum in no packfile; a blob that fails
+ * Decode, whose decoded length is not the recorded Length (CDC_E_MISMATCH) or
+ * whose SHA-256 differs (CDC_E_MISMATCH) fails every file that uses it; a
+ * destination that cannot be created or written is CDC_E_IO.  A failed file
+ * is not written, and what earlier pieces of it wrote is removed.  A file
+ * with a path is created with O_CREAT|O_TRUNC (an empty file empty) and
+ * on_file is called once for it, after its last byte was written or with
+ * its failure.  With path == NULL on_file is called once per piece with that
+ * piece's bytes (valid during the call only); a file's last call carries its
+ * final status, and a caller that was handed earlier pieces of a file that
+ * then fails drops them.  on_file (may be NULL) is called from one library
+ * thread at a time.  Returns CDC_OK, or the run's own first failure (a device
+ * error); *stats may be NULL. */
+int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
+                      cdc_restore_stats *stats);
+void cdc_restore_free(cdc_restore *r);
+
 /* The library's host SHA-256 (x86 SHA extensions when the CPU has them;
  * force_scalar != 0 takes the portable path).  cdc_sha256_accelerated: 1 if
  * the SHA extensions are in use. */

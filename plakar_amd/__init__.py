@@ -10,7 +10,8 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
     plakar_amd.device      device-resident batches (torch tensors in HBM)
     plakar_amd.encode      Repository.Encode on the device (DeviceEncoder)
     plakar_amd.decode      Repository.Decode and the blob check on the device (DeviceDecoder)
+    plakar_amd.restore     packfiles and object records back to files (RestoreSession, restore_files)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "build"]

@@ -31,6 +31,7 @@ CDC_E_NO_DEVICE = -11
 CDC_E_AUTH = -12
 CDC_E_CORRUPT = -13
 CDC_E_MISMATCH = -14
+CDC_E_NOTFOUND = -15
 
 
 class cdc_opts(ctypes.Structure):
@@ -79,6 +80,42 @@ class cdc_backup_stats(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("fill_s", "drain_s", "chain_s")] + [("chain_bytes", ctypes.c_uint64)]
 
 
+class cdc_packfile_footer(ctypes.Structure):
+    _fields_ = [("version", ctypes.c_uint32), ("count", ctypes.c_uint32), ("timestamp", ctypes.c_int64),
+                ("index_offset", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("index_checksum", ctypes.c_uint8 * 32)]
+
+
+class cdc_packfile_row(ctypes.Structure):
+    _fields_ = [("checksum", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint32), ("length", ctypes.c_uint32),
+                ("type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+class cdc_restore_opts(ctypes.Structure):
+    _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_void_p), ("verify", ctypes.c_int),
+                ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64)]
+
+
+class cdc_restore_file(ctypes.Structure):
+    _fields_ = [("path", ctypes.c_char_p), ("nchunks", ctypes.c_uint64), ("checksums", ctypes.c_void_p),
+                ("lengths", ctypes.c_void_p)]
+
+
+class cdc_restore_result(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_int), ("status", ctypes.c_int), ("size", ctypes.c_uint64),
+                ("piece", ctypes.c_uint32), ("pieces", ctypes.c_uint32), ("data", ctypes.POINTER(ctypes.c_uint8)),
+                ("data_offset", ctypes.c_uint64), ("data_len", ctypes.c_uint64)]
+
+
+class cdc_restore_stats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("files", "failed_files", "bytes", "segments", "distinct_blobs",
+                                               "decoded_blobs", "encoded_bytes", "decoded_bytes", "batches", "batches_identity",
+                                               "pieces")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "assemble_s", "d2h_s",
+                                               "write_s", "wall_s")]
+
+
+RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_restore_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 
@@ -183,6 +220,19 @@ SIGNATURES = {
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                         ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32),
                                         ctypes.c_void_p]),
+    "cdc_packfile_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, _P(cdc_packfile_footer),
+                                          _P(cdc_packfile_row), ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_assemble_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                           _P(ctypes.c_uint64), _P(ctypes.c_uint64), ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "cdc_debug_set_assemble_policy": (ctypes.c_int, [ctypes.c_int]),
+    "cdc_restore_default_opts": (None, [_P(cdc_restore_opts)]),
+    "cdc_restore_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_restore_opts), _P(ctypes.c_void_p)]),
+    "cdc_restore_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_restore_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_restore_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, RESTORE_FILE_FN,
+                                         ctypes.c_void_p, _P(cdc_restore_stats)]),
+    "cdc_restore_free": (None, [ctypes.c_void_p]),
     "cdc_set_debug_mode": (ctypes.c_int, [ctypes.c_int]),
     "cdc_gear_is_placeholder": (ctypes.c_int, []),
     "cdc_set_maskl_index_mode": (ctypes.c_int, [ctypes.c_int]),

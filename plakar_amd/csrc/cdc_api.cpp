@@ -781,6 +781,7 @@ const char *cdc_strerror(int s)
     case CDC_E_AUTH: return "a GCM tag did not verify";
     case CDC_E_CORRUPT: return "malformed encoded stream";
     case CDC_E_MISMATCH: return "decoded blob does not match its checksum";
+    case CDC_E_NOTFOUND: return "chunk is in no registered packfile";
     default: return "unknown status";
     }
 }

@@ -47,6 +47,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -698,6 +699,55 @@ static bool bad_args(int device, const void *d_in, const uint64_t *offsets, cons
     return device < 0 || device >= 64 || (n && (!d_in || !offsets || !lens || !status));
 }
 
+// The hashing half of cdc_check_device, over blobs that cdc_decode_device left
+// at d_scratch + oo[i] (n + 1 offsets): status[i] == CDC_OK becomes
+// CDC_E_MISMATCH where the SHA-256 differs from checksums[32 i].  The plaintext
+// is only read.  Synchronous on `stream`.
+static int check_decoded(int device, const uint8_t *d_scratch, const uint64_t *oo, uint32_t n,
+                         const uint8_t *checksums, int32_t *status, void *stream)
+{
+    int st;
+    // SHA-256 of every blob on the device (k_chunk_digest hashes an empty chunk
+    // to SHA-256("")); a blob that did not decode is an empty cut whose row is
+    // ignored.  Empty cuts sit at offset 0, and when nothing decoded at all
+    // the hashed buffer is 16 bytes of the workspace, not the caller's.
+    const size_t m = n;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align16(off + bytes);
+        return o;
+    };
+    const size_t o_cuts = take(m * sizeof(cdc_cut)), o_want = take(m * 32), h_bytes = off;
+    const size_t o_got = take(m * 32), o_diff = take(m * 4), o_dummy = take(16);
+    WsCache &C = g_cws[device];
+    std::lock_guard<std::mutex> lk(C.mu);
+    st = ws_reserve(C, off, h_bytes + m * 4);
+    if (st != CDC_OK) return st;
+    cdc_cut *cuts = reinterpret_cast<cdc_cut *>(C.hp + o_cuts);
+    for (uint32_t b = 0; b < n; ++b) {
+        const uint64_t len = status[b] == CDC_OK ? oo[b + 1] - oo[b] : 0;
+        cuts[b] = cdc_cut{len ? oo[b] : 0, uint32_t(len), 0};
+    }
+    std::memcpy(C.hp + o_want, checksums, m * 32);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemcpyAsync(C.p, C.hp, h_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
+    st = cdc_chunk_digests_device_async(device, oo[n] ? d_scratch : C.p + o_dummy, oo[n],
+                                        reinterpret_cast<const cdc_cut *>(C.p + o_cuts), m, nullptr, C.p + o_got,
+                                        nullptr, stream);
+    if (st != CDC_OK) return st;
+    hipLaunchKernelGGL(k_check_cmp, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, s, C.p + o_got, C.p + o_want,
+                       reinterpret_cast<uint32_t *>(C.p + o_diff), uint32_t(m));
+    uint32_t *diff = reinterpret_cast<uint32_t *>(C.hp + h_bytes);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(diff, C.p + o_diff, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return CDC_E_DEVICE;
+    for (uint32_t b = 0; b < n; ++b)
+        if (status[b] == CDC_OK && diff[b]) status[b] = CDC_E_MISMATCH;
+    return CDC_OK;
+}
+
 }  // namespace dec
 
 using namespace dec;
@@ -852,43 +902,22 @@ extern "C" int cdc_check_device(int device, const void *d_in, const uint64_t *of
                                status, stream);
     if (needed) *needed = oo[n];
     if (st != CDC_OK) return st;
-    // SHA-256 of every blob on the device (k_chunk_digest hashes an empty chunk
-    // to SHA-256("")); a blob that did not decode is an empty cut whose row is
-    // ignored.  Empty cuts sit at offset 0, and when nothing decoded at all
-    // the hashed buffer is 16 bytes of the workspace, not the caller's.
-    const size_t m = n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align16(off + bytes);
-        return o;
-    };
-    const size_t o_cuts = take(m * sizeof(cdc_cut)), o_want = take(m * 32), h_bytes = off;
-    const size_t o_got = take(m * 32), o_diff = take(m * 4), o_dummy = take(16);
-    WsCache &C = g_cws[device];
-    std::lock_guard<std::mutex> lk(C.mu);
-    st = ws_reserve(C, off, h_bytes + m * 4);
-    if (st != CDC_OK) return st;
-    cdc_cut *cuts = reinterpret_cast<cdc_cut *>(C.hp + o_cuts);
-    for (uint32_t b = 0; b < n; ++b) {
-        const uint64_t len = status[b] == CDC_OK ? oo[b + 1] - oo[b] : 0;
-        cuts[b] = cdc_cut{len ? oo[b] : 0, uint32_t(len), 0};
-    }
-    std::memcpy(C.hp + o_want, checksums, m * 32);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemcpyAsync(C.p, C.hp, h_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
-    st = cdc_chunk_digests_device_async(device, oo[n] ? d_scratch : C.p + o_dummy, oo[n],
-                                        reinterpret_cast<const cdc_cut *>(C.p + o_cuts), m, nullptr, C.p + o_got,
-                                        nullptr, stream);
-    if (st != CDC_OK) return st;
-    hipLaunchKernelGGL(k_check_cmp, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, s, C.p + o_got, C.p + o_want,
-                       reinterpret_cast<uint32_t *>(C.p + o_diff), uint32_t(m));
-    uint32_t *diff = reinterpret_cast<uint32_t *>(C.hp + h_bytes);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(diff, C.p + o_diff, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return CDC_E_DEVICE;
-    for (uint32_t b = 0; b < n; ++b)
-        if (status[b] == CDC_OK && diff[b]) status[b] = CDC_E_MISMATCH;
-    return CDC_OK;
+    return check_decoded(device, d_scratch, oo.data(), n, checksums, status, stream);
+}
+
+// cdc_restore.cpp's seam: Decode and, with checksums, the check, in one call
+// that reports the offsets and the statuses and leaves the plaintext in d_out.
+int cdc::decode_checked(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                        int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *out_offsets, int32_t *status, void *stream, double *decode_s, double *verify_s)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    int st = cdc_decode_device(device, d_in, offsets, lens, n, compressed, key, d_out, out_cap, out_offsets, status,
+                               stream);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (decode_s) *decode_s += std::chrono::duration<double>(t1 - t0).count();
+    if (st != CDC_OK || !checksums || n == 0) return st;
+    st = check_decoded(device, d_out, out_offsets, n, checksums, status, stream);
+    if (verify_s) *verify_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return st;
 }

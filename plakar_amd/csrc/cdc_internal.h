@@ -207,6 +207,14 @@ struct Sha256 {
 void sha256(const void *data, size_t n, uint8_t out[32], bool force_scalar = false);
 bool sha256_accelerated();
 
+// cdc_decode.hip: cdc_decode_device, then (checksums != NULL) cdc_check_device's
+// hash-and-compare over the plaintext it left in d_out, which stays there:
+// out_offsets as cdc_decode_device, status[i] as cdc_check_device.  The seconds
+// of each half are added to *decode_s / *verify_s (may be NULL).
+int decode_checked(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                   int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_out, uint64_t out_cap,
+                   uint64_t *out_offsets, int32_t *status, void *stream, double *decode_s, double *verify_s);
+
 // cdc_packer.cpp: in-place serialization for the backup pipeline's sinks
 int packer_seal(cdc_packer *p, int64_t timestamp, const uint8_t **data, uint64_t *len);
 void packer_reserve(cdc_packer *p, uint64_t max_blob);

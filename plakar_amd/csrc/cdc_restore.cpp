@@ -1,0 +1,699 @@
+// cdc_restore_*: packfiles in, files out (include/plakar_cdc.h, "restore").
+//
+// The reference restores one chunk at a time: snapshot/restore.go:103-110 opens
+// a reader per file, snapshot/vfs/vfilep.go:58-122 serves Read by one
+// repo.GetBlob per chunk, repository/repository.go:449-466 looks the checksum
+// up (GetSubpartForBlob) and repository.go:407-429 does one ranged packfile
+// read and one Decode; a chunk that occurs twice is decoded twice and nothing
+// is verified.  Here a run is a pipeline over batches of output bytes planned
+// up front (restore_plan.h), three stages on three threads and three streams:
+//
+//   reader   gathers the batch's distinct encoded blobs into a pinned arena
+//            (memcpy or pread, on `writers` threads) and uploads it;
+//   device   (the calling thread) Decode + check over the distinct blobs, then
+//            cdc_assemble_device into the batch's output image, or nothing
+//            when the plaintext buffer already is that image;
+//   writer   downloads the image into a pinned slot, pwrites every piece
+//            (`writers` threads) and makes the callbacks.
+//
+// Two input slots and two output slots rotate: batch k + 1 is read and
+// uploaded while batch k is on the device and batch k - 1 is downloaded and
+// written.  Decode is synchronous and holds the per-device workspace, so the
+// device stages of two batches never overlap.
+#include <fcntl.h>
+#include <hip/hip_runtime.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "cdc_internal.h"
+#include "restore_plan.h"
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+struct Sum {
+    uint8_t b[32];
+    bool operator==(const Sum &o) const { return std::memcmp(b, o.b, 32) == 0; }
+};
+struct SumHash {  // the checksums are SHA-256: any eight bytes are a hash
+    size_t operator()(const Sum &s) const
+    {
+        uint64_t v;
+        std::memcpy(&v, s.b, 8);
+        return size_t(v);
+    }
+};
+struct Pack {
+    const uint8_t *mem;  // the caller's buffer, or NULL: read from path
+    std::string path;
+    uint64_t len;
+};
+struct Loc {
+    uint32_t pack, offset, length;
+};
+
+static void sha_cb(const void *data, size_t n, uint8_t out[32]) { cdc::sha256(data, n, out); }
+
+static bool pread_all(int fd, uint8_t *dst, uint64_t len, uint64_t off)
+{
+    while (len) {
+        const ssize_t r = pread(fd, dst, len, off_t(off));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        dst += r;
+        off += uint64_t(r);
+        len -= uint64_t(r);
+    }
+    return true;
+}
+
+static bool pwrite_all(int fd, const uint8_t *src, uint64_t len, uint64_t off)
+{
+    while (len) {
+        const ssize_t r = pwrite(fd, src, len, off_t(off));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        src += r;
+        off += uint64_t(r);
+        len -= uint64_t(r);
+    }
+    return true;
+}
+
+template <class F>
+static void parallel_for(int threads, size_t n, F fn)
+{
+    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
+    if (t <= 1) {
+        for (size_t i = 0; i < n; ++i) fn(i);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+}
+
+static int grow_dev(uint8_t *&p, size_t &cap, size_t need)
+{
+    need = std::max<size_t>(need, 16);
+    if (cap >= need) return CDC_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&p), need) != hipSuccess) return CDC_E_NOMEM;
+    cap = need;
+    return CDC_OK;
+}
+
+static int grow_pin(uint8_t *&p, size_t &cap, size_t need)
+{
+    need = std::max<size_t>(need, 16);
+    if (cap >= need) return CDC_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipHostMalloc(reinterpret_cast<void **>(&p), need, hipHostMallocDefault) != hipSuccess) return CDC_E_NOMEM;
+    cap = need;
+    return CDC_OK;
+}
+
+struct InSlot {   // reader -> device stage
+    uint8_t *h = nullptr, *d = nullptr;
+    size_t hcap = 0, dcap = 0;
+    std::vector<uint64_t> eoff, elen;  // the batch's encoded blobs in the arena
+    std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
+};
+struct OutSlot {  // device stage -> writer
+    uint8_t *d = nullptr, *h = nullptr;
+    size_t dcap = 0, hcap = 0;
+};
+
+}  // namespace
+
+struct cdc_restore {
+    int device = 0;
+    cdc_restore_opts o{};
+    std::vector<uint8_t> key;
+    std::vector<Pack> packs;
+    std::unordered_map<Sum, uint32_t, SumHash> index;  // checksum -> blob id
+    std::vector<Loc> locs;                             // by blob id
+    std::vector<Sum> sums;                             // by blob id
+    hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stages, download
+    InSlot in[2];
+    OutSlot out[2];
+    uint8_t *plain = nullptr;
+    size_t plain_cap = 0;
+    std::mutex run_mu;
+};
+
+namespace {
+
+struct Run {
+    cdc_restore *R;
+    const cdc_restore_file *files;
+    int n;
+    cdc_restore_file_fn on_file;
+    void *ctx;
+    std::vector<rplan::Batch> batches;
+    std::vector<std::vector<uint32_t>> fblob;  // planned file -> its chunks' blob ids
+    std::vector<rplan::File> pf;
+    std::vector<int> pidx;                     // planned file -> index in files
+    std::unique_ptr<std::atomic<int>[]> fstatus;
+    std::vector<uint8_t> created, reported;
+    std::vector<uint64_t> fsize;
+    std::vector<uint32_t> fpieces, fseen;
+    // the stages' hand-offs: counts of batches past each point
+    std::mutex mu;
+    std::condition_variable cv;
+    int uploaded = 0, consumed = 0, assembled = 0, written = 0;
+    int fail = CDC_OK;
+    cdc_restore_stats st{};
+    double read_s = 0, h2d_s = 0, decode_s = 0, verify_s = 0, assemble_s = 0, d2h_s = 0, write_s = 0;
+
+    void fail_file(int fi, int status)
+    {
+        int ok = CDC_OK;
+        fstatus[fi].compare_exchange_strong(ok, status);
+    }
+    // Wait until `counter` reaches `want`; false when the run has failed.
+    bool wait_for(const int &counter, int want)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return counter >= want || fail != CDC_OK; });
+        return fail == CDC_OK;
+    }
+    void advance(int &counter)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            ++counter;
+        }
+        cv.notify_all();
+    }
+    void abort_run(int status)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (fail == CDC_OK) fail = status;
+        }
+        cv.notify_all();
+    }
+    void report(int fi, int status, uint32_t piece, uint32_t pieces, const uint8_t *data, uint64_t off, uint64_t len)
+    {
+        if (!on_file) return;
+        cdc_restore_result r{};
+        r.index = fi;
+        r.status = status;
+        r.size = fsize[fi];
+        r.piece = piece;
+        r.pieces = pieces;
+        r.data = data;
+        r.data_offset = off;
+        r.data_len = len;
+        on_file(ctx, &r);
+    }
+};
+
+// ---- reader stage ---------------------------------------------------------------
+static void reader_stage(Run &X)
+{
+    cdc_restore *R = X.R;
+    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    for (int k = 0; k < int(X.batches.size()); ++k) {
+        if (!X.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
+        const rplan::Batch &B = X.batches[k];
+        InSlot &S = R->in[k & 1];
+        const size_t nb = B.blobs.size();
+        auto t0 = Clock::now();
+        S.eoff.assign(nb, 0);
+        S.elen.assign(nb, 0);
+        S.pre.assign(nb, CDC_OK);
+        uint64_t total = 0;
+        std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
+        for (size_t b = 0; b < nb; ++b) {
+            const Loc &L = R->locs[B.blobs[b].id];
+            S.eoff[b] = total;
+            S.elen[b] = L.length;
+            total += L.length;
+            const Pack &P = R->packs[L.pack];
+            if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
+        }
+        int st = grow_pin(S.h, S.hcap, total);
+        if (st == CDC_OK) st = grow_dev(S.d, S.dcap, total);
+        if (st != CDC_OK) {
+            for (auto &f : fds)
+                if (f.second >= 0) close(f.second);
+            return X.abort_run(st);
+        }
+        parallel_for(R->o.writers, nb, [&](size_t b) {
+            const Loc &L = R->locs[B.blobs[b].id];
+            const Pack &P = R->packs[L.pack];
+            if (P.mem) {
+                std::memcpy(S.h + S.eoff[b], P.mem + L.offset, L.length);
+                return;
+            }
+            const int fd = fds.find(L.pack)->second;
+            if (fd < 0 || !pread_all(fd, S.h + S.eoff[b], L.length, L.offset)) S.pre[b] = CDC_E_IO;
+        });
+        for (auto &f : fds)
+            if (f.second >= 0) close(f.second);
+        X.read_s += since(t0);
+        X.st.encoded_bytes += total;
+        t0 = Clock::now();
+        if (total && (hipMemcpyAsync(S.d, S.h, total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
+                      hipStreamSynchronize(R->stream[0]) != hipSuccess))
+            return X.abort_run(CDC_E_DEVICE);
+        X.h2d_s += since(t0);
+        X.advance(X.uploaded);
+    }
+}
+
+// ---- device stage (the calling thread) --------------------------------------------
+static void device_stage(Run &X)
+{
+    cdc_restore *R = X.R;
+    std::vector<uint64_t> oo, pos, so, sl, sd;
+    std::vector<int32_t> bst;
+    std::vector<uint8_t> want;
+    for (int k = 0; k < int(X.batches.size()); ++k) {
+        if (!X.wait_for(X.uploaded, k + 1) || !X.wait_for(X.written, k - 1)) return;
+        const rplan::Batch &B = X.batches[k];
+        InSlot &I = R->in[k & 1];
+        OutSlot &O = R->out[k & 1];
+        const uint32_t nb = uint32_t(B.blobs.size());
+        int st = grow_dev(O.d, O.dcap, B.out_bytes);
+        if (st == CDC_OK) st = grow_pin(O.h, O.hcap, B.out_bytes);
+        bool direct = B.identity;  // decode straight into the output image
+        if (st == CDC_OK && !direct) st = grow_dev(R->plain, R->plain_cap, B.plain_bytes);
+        if (st != CDC_OK) return X.abort_run(st);
+        oo.assign(size_t(nb) + 1, 0);
+        bst.assign(std::max<uint32_t>(nb, 1), CDC_OK);
+        if (R->o.verify) {
+            want.resize(size_t(nb) * 32 + 1);
+            for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], R->sums[B.blobs[b].id].b, 32);
+        }
+        for (uint32_t b = 0; b < nb; ++b)
+            if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
+        const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
+        const uint8_t *sums = R->o.verify ? want.data() : nullptr;
+        st = cdc::decode_checked(R->device, I.d, I.eoff.data(), I.elen.data(), nb, R->o.compress, key, sums,
+                                 direct ? O.d : R->plain, B.plain_bytes, oo.data(), bst.data(), R->stream[1],
+                                 &X.decode_s, &X.verify_s);
+        pos.assign(oo.begin(), oo.end() - 1);
+        uint64_t plain_used = oo[nb];
+        if (st == CDC_E_NOSPACE) {
+            // Some blob decodes to more than its recorded Length, by an amount
+            // only its own bytes bound.  Decode the batch's blobs one by one,
+            // each into the room its Length gives it: the ones that fit come
+            // out, the others are the mismatch.  (A slow path: it runs only
+            // for a batch that holds such a blob.)
+            direct = false;
+            st = grow_dev(R->plain, R->plain_cap, B.plain_bytes);
+            for (uint32_t b = 0; b < nb && st == CDC_OK; ++b) {
+                uint64_t o2[2] = {0, 0};
+                st = cdc::decode_checked(R->device, I.d, &I.eoff[b], &I.elen[b], 1, R->o.compress, key,
+                                         sums ? sums + size_t(b) * 32 : nullptr, R->plain + B.blobs[b].off,
+                                         B.blobs[b].len, o2, &bst[b], R->stream[1], &X.decode_s, &X.verify_s);
+                if (st == CDC_E_NOSPACE) {
+                    st = CDC_OK;
+                    bst[b] = CDC_E_MISMATCH;
+                    o2[1] = 0;
+                }
+                pos[b] = B.blobs[b].off;
+                if (bst[b] == CDC_OK && o2[1] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
+                X.st.decoded_bytes += o2[1];
+            }
+            plain_used = B.plain_bytes;
+        } else if (st == CDC_OK) {
+            for (uint32_t b = 0; b < nb; ++b)
+                if (bst[b] == CDC_OK && oo[b + 1] - oo[b] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
+            X.st.decoded_bytes += oo[nb];
+        }
+        if (st != CDC_OK) return X.abort_run(st);
+        bool bad = false;
+        for (uint32_t b = 0; b < nb; ++b) {
+            if (I.pre[b] != CDC_OK) bst[b] = I.pre[b];
+            bad = bad || bst[b] != CDC_OK;
+        }
+        X.advance(X.consumed);
+        if (bad)
+            for (const rplan::Piece &P : B.pieces)
+                for (uint64_t s = P.seg0; s < P.seg0 + P.nchunks; ++s)
+                    if (bst[B.segs[s].blob] != CDC_OK) {
+                        X.fail_file(X.pidx[P.file], bst[B.segs[s].blob]);
+                        break;
+                    }
+        if (direct && !bad) {
+            ++X.st.batches_identity;
+        } else {
+            const auto t0 = Clock::now();
+            bool ok = true;
+            if (direct) {  // the plaintext sits compacted in the image: move it out of the way first
+                st = grow_dev(R->plain, R->plain_cap, plain_used);
+                if (st != CDC_OK) return X.abort_run(st);
+                ok = !plain_used ||
+                     hipMemcpyAsync(R->plain, O.d, plain_used, hipMemcpyDeviceToDevice, R->stream[1]) == hipSuccess;
+            }
+            so.clear();
+            sl.clear();
+            sd.clear();
+            for (const rplan::Segment &S : B.segs) {
+                if (bst[S.blob] != CDC_OK) continue;  // its files have failed; their bytes are not delivered
+                so.push_back(pos[S.blob]);
+                sl.push_back(S.len);
+                sd.push_back(S.dst_off);
+            }
+            if (ok && !so.empty())
+                st = cdc_assemble_device(R->device, R->plain, plain_used, so.data(), sl.data(), sd.data(), so.size(), O.d,
+                                         B.out_bytes, R->stream[1]);
+            if (st != CDC_OK) return X.abort_run(st);
+            if (!ok || hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+            X.assemble_s += since(t0);
+        }
+        X.advance(X.assembled);
+    }
+}
+
+// ---- writer stage -------------------------------------------------------------------
+static void write_piece(Run &X, const rplan::Piece &P, const uint8_t *image)
+{
+    const int fi = X.pidx[P.file];
+    const char *path = X.files[fi].path;
+    if (!path || X.fstatus[fi].load() != CDC_OK) return;
+    const int fd = open(path, P.first ? O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC : O_WRONLY | O_CLOEXEC, 0644);
+    if (fd < 0) return X.fail_file(fi, CDC_E_IO);
+    if (P.first) X.created[fi] = 1;
+    const bool ok = pwrite_all(fd, image + P.dst_off, P.len, P.file_off);
+    if (close(fd) != 0 || !ok) X.fail_file(fi, CDC_E_IO);
+}
+
+static void writer_stage(Run &X)
+{
+    cdc_restore *R = X.R;
+    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    for (int k = 0; k < int(X.batches.size()); ++k) {
+        if (!X.wait_for(X.assembled, k + 1)) return;
+        const rplan::Batch &B = X.batches[k];
+        OutSlot &O = R->out[k & 1];
+        auto t0 = Clock::now();
+        if (B.out_bytes && (hipMemcpyAsync(O.h, O.d, B.out_bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
+                            hipStreamSynchronize(R->stream[2]) != hipSuccess))
+            return X.abort_run(CDC_E_DEVICE);
+        X.d2h_s += since(t0);
+        t0 = Clock::now();
+        parallel_for(R->o.writers, B.pieces.size(), [&](size_t i) { write_piece(X, B.pieces[i], O.h); });
+        X.write_s += since(t0);
+        for (const rplan::Piece &P : B.pieces) {
+            const int fi = X.pidx[P.file];
+            const int s = X.fstatus[fi].load();
+            const char *path = X.files[fi].path;
+            if (path) {
+                if (s != CDC_OK && X.created[fi]) {  // what earlier pieces wrote goes with the failure
+                    unlink(path);
+                    X.created[fi] = 0;
+                }
+                if (P.last) {
+                    X.reported[fi] = 1;
+                    X.report(fi, s, 0, 1, nullptr, 0, 0);
+                }
+            } else {
+                if (P.last) X.reported[fi] = 1;
+                X.report(fi, s, X.fseen[fi]++, X.fpieces[fi], s == CDC_OK ? O.h + P.dst_off : nullptr, P.file_off,
+                         s == CDC_OK ? P.len : 0);
+            }
+        }
+        X.advance(X.written);
+    }
+}
+
+static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
+                     cdc_restore_stats *stats)
+{
+    const auto w0 = Clock::now();
+    Run X{};
+    X.R = R;
+    X.files = files;
+    X.n = n;
+    X.on_file = on_file;
+    X.ctx = ctx;
+    X.fstatus.reset(new std::atomic<int>[size_t(std::max(n, 1))]);
+    X.created.assign(size_t(n), 0);
+    X.reported.assign(size_t(n), 0);
+    X.fsize.assign(size_t(n), 0);
+    X.fpieces.assign(size_t(n), 0);
+    X.fseen.assign(size_t(n), 0);
+    // the locator: every chunk's blob id, or CDC_E_NOTFOUND for the file
+    for (int i = 0; i < n; ++i) {
+        X.fstatus[i].store(CDC_OK);
+        const cdc_restore_file &F = files[i];
+        std::vector<uint32_t> ids(size_t(F.nchunks));
+        for (uint64_t c = 0; c < F.nchunks; ++c) {
+            Sum s;
+            std::memcpy(s.b, F.checksums + 32 * c, 32);
+            const auto it = R->index.find(s);
+            if (it == R->index.end()) {
+                X.fstatus[i].store(CDC_E_NOTFOUND);
+                break;
+            }
+            ids[size_t(c)] = it->second;
+            X.fsize[i] += F.lengths[c];
+        }
+        if (X.fstatus[i].load() != CDC_OK) continue;
+        X.fblob.push_back(std::move(ids));
+        X.pidx.push_back(i);
+    }
+    for (size_t p = 0; p < X.pidx.size(); ++p)
+        X.pf.push_back(rplan::File{files[X.pidx[p]].nchunks, X.fblob[p].data(), files[X.pidx[p]].lengths});
+    rplan::plan(X.pf.data(), X.pf.size(), R->o.batch_bytes, X.batches);
+    std::vector<bool> used(R->locs.size(), false);
+    for (const rplan::Batch &B : X.batches) {
+        X.st.bytes += B.out_bytes;
+        X.st.segments += B.segs.size();
+        X.st.decoded_blobs += B.blobs.size();
+        for (const rplan::Blob &b : B.blobs)
+            if (!used[b.id]) {
+                used[b.id] = true;
+                ++X.st.distinct_blobs;
+            }
+        X.st.pieces += B.pieces.size();
+        for (const rplan::Piece &P : B.pieces) ++X.fpieces[X.pidx[P.file]];
+    }
+    X.st.batches = X.batches.size();
+    X.st.files = uint64_t(n);
+    for (int i = 0; i < n; ++i)
+        if (X.fstatus[i].load() != CDC_OK) {
+            X.reported[i] = 1;
+            X.report(i, X.fstatus[i].load(), 0, 1, nullptr, 0, 0);
+        }
+    if (!X.batches.empty()) {
+        if (hipSetDevice(R->device) != hipSuccess) return CDC_E_DEVICE;
+        auto guarded = [&X](void (*stage)(Run &)) {
+            try {
+                stage(X);
+            } catch (...) {
+                X.abort_run(CDC_E_NOMEM);
+            }
+        };
+        std::thread reader(guarded, reader_stage);
+        std::thread writer(guarded, writer_stage);
+        guarded(device_stage);
+        reader.join();
+        writer.join();
+    }
+    // a run that broke off: the files it did not finish fail with its status
+    for (int i = 0; i < n; ++i) {
+        if (!X.reported[i]) {
+            if (files[i].path && X.created[i]) unlink(files[i].path);
+            X.fstatus[i].store(X.fail != CDC_OK ? X.fail : CDC_E_DEVICE);
+            X.report(i, X.fstatus[i].load(), 0, 1, nullptr, 0, 0);
+        }
+        X.st.failed_files += X.fstatus[i].load() != CDC_OK;
+    }
+    X.st.read_s = X.read_s;
+    X.st.h2d_s = X.h2d_s;
+    X.st.decode_s = X.decode_s;
+    X.st.verify_s = X.verify_s;
+    X.st.assemble_s = X.assemble_s;
+    X.st.d2h_s = X.d2h_s;
+    X.st.write_s = X.write_s;
+    X.st.wall_s = since(w0);
+    if (stats) *stats = X.st;
+    return X.fail;
+}
+
+static int add_rows(cdc_restore *R, Pack &&P, const std::vector<cdc_packfile_row> &rows)
+{
+    const uint32_t pack = uint32_t(R->packs.size());
+    R->packs.push_back(std::move(P));
+    for (const cdc_packfile_row &r : rows) {
+        if (r.type != rplan::kTypeChunk) continue;
+        Sum s;
+        std::memcpy(s.b, r.checksum, 32);
+        if (R->index.emplace(s, uint32_t(R->locs.size())).second) {
+            R->locs.push_back(Loc{pack, r.offset, r.length});
+            R->sums.push_back(s);
+        }
+    }
+    return CDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cdc_packfile_index(const uint8_t *bytes, uint64_t len, cdc_packfile_footer *footer, cdc_packfile_row *rows,
+                       uint64_t cap, uint64_t *needed)
+{
+    if (!footer || (!bytes && len) || (!rows && cap)) return CDC_E_INVALID;
+    if (needed) *needed = 0;
+    const int st = rplan::parse_packfile(bytes, len, sha_cb, footer, rows, cap);
+    if (st != CDC_OK) return st;
+    if (needed) *needed = footer->count;
+    return footer->count > cap ? CDC_E_NOSPACE : CDC_OK;
+}
+
+void cdc_restore_default_opts(cdc_restore_opts *out)
+{
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->verify = 1;
+}
+
+int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out)
+{
+    if (!opts || !out) return CDC_E_INVALID;
+    *out = nullptr;
+    if (device < 0 || device >= 64 || opts->writers < 0 || opts->writers > 256) return CDC_E_INVALID;
+    if (!cdc::device_count_initialised()) return CDC_E_NOT_INIT;
+    auto *r = new (std::nothrow) cdc_restore();
+    if (!r) return CDC_E_NOMEM;
+    try {
+        r->device = device;
+        r->o = *opts;
+        if (opts->key) r->key.assign(opts->key, opts->key + 32);
+        r->o.key = nullptr;
+        if (!r->o.writers) r->o.writers = 8;
+        if (!r->o.batch_bytes) r->o.batch_bytes = 256ull << 20;
+    } catch (...) {
+        delete r;
+        return CDC_E_NOMEM;
+    }
+    bool ok = hipSetDevice(device) == hipSuccess;
+    for (int i = 0; i < 3; ++i) ok = ok && hipStreamCreateWithFlags(&r->stream[i], hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        cdc_restore_free(r);
+        return CDC_E_DEVICE;
+    }
+    *out = r;
+    return CDC_OK;
+}
+
+int cdc_restore_add_packfile(cdc_restore *r, const uint8_t *bytes, uint64_t len)
+{
+    if (!r || (!bytes && len)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(r->run_mu);
+    try {
+        cdc_packfile_footer f;
+        int st = rplan::parse_packfile(bytes, len, sha_cb, &f, nullptr, 0);
+        if (st != CDC_OK) return st;
+        std::vector<cdc_packfile_row> rows(f.count);
+        st = rplan::parse_packfile(bytes, len, sha_cb, &f, rows.data(), rows.size());
+        if (st != CDC_OK) return st;
+        return add_rows(r, Pack{bytes, std::string(), len}, rows);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_restore_add_packfile_path(cdc_restore *r, const char *path)
+{
+    if (!r || !path) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(r->run_mu);
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return CDC_E_IO;
+    int st = CDC_OK;
+    try {
+        struct stat sb;
+        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+            st = CDC_E_IO;
+        } else if (uint64_t(sb.st_size) < rplan::kFooterBytes) {
+            st = CDC_E_CORRUPT;
+        } else {
+            const uint64_t len = uint64_t(sb.st_size);
+            uint8_t tail[rplan::kFooterBytes];
+            cdc_packfile_footer f;
+            if (!pread_all(fd, tail, sizeof(tail), len - sizeof(tail))) st = CDC_E_IO;
+            if (st == CDC_OK) st = rplan::parse_footer(tail, len, &f);
+            if (st == CDC_OK) {
+                std::vector<uint8_t> idx(size_t(rplan::kRowBytes * f.count) + 1);
+                std::vector<cdc_packfile_row> rows(f.count);
+                if (!pread_all(fd, idx.data(), rplan::kRowBytes * f.count, f.index_offset)) st = CDC_E_IO;
+                if (st == CDC_OK) st = rplan::parse_index(idx.data(), f, sha_cb, rows.data(), rows.size());
+                if (st == CDC_OK) st = add_rows(r, Pack{nullptr, std::string(path), len}, rows);
+            }
+        }
+    } catch (...) {
+        st = CDC_E_NOMEM;
+    }
+    close(fd);
+    return st;
+}
+
+int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
+                      cdc_restore_stats *stats)
+{
+    if (!r || n < 0 || (n && !files)) return CDC_E_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(r->run_mu);
+    try {
+        return run_files(r, files, n, on_file, ctx, stats);
+    } catch (const std::bad_alloc &) {
+        return CDC_E_NOMEM;
+    }
+}
+
+void cdc_restore_free(cdc_restore *r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    for (auto &s : r->stream)
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+    for (InSlot &s : r->in) {
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.d) (void)hipFree(s.d);
+    }
+    for (OutSlot &s : r->out) {
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.d) (void)hipFree(s.d);
+    }
+    if (r->plain) (void)hipFree(r->plain);
+    if (!r->key.empty()) std::memset(r->key.data(), 0, r->key.size());
+    delete r;
+}
+
+}  // extern "C"

@@ -1,0 +1,183 @@
+"""Restore on the device: packfiles and object records in, files out.
+
+The reference reads a file back chunk by chunk (snapshot/restore.go:103-110,
+snapshot/vfs/vfilep.go:58-122: one repo.GetBlob per chunk; repository/
+repository.go:449-466 and 407-429: a state lookup, one ranged packfile read and
+one Decode each).  cdc_restore_files does it per batch of output bytes: every
+distinct blob of the batch is read and decoded once (and, with verify, hashed
+and compared with its checksum), cdc_assemble_device copies it to every place
+it occurs, and writer threads put the files on disk.  Every call goes through
+the C ABI (cdc_packfile_index, cdc_assemble_device, cdc_restore_*)."""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, ensure_init, lib
+
+DEFAULT_BATCH_BYTES = 256 << 20
+
+
+def packfile_index(data):
+    """packfile.NewFromBytes (packfile/packfile.go:152-239) of a serialised
+    packfile: (footer, rows), footer a dict of version, timestamp, count,
+    index_offset and index_checksum, rows a list of (type, checksum, offset,
+    length).  Raises CdcError(CDC_E_CORRUPT) for a malformed packfile."""
+    data = bytes(data)
+    L = lib()
+    f = _lib.cdc_packfile_footer()
+    need = ctypes.c_uint64()
+    rc = L.cdc_packfile_index(data, len(data), ctypes.byref(f), None, 0, ctypes.byref(need))
+    rows = None
+    if rc == _lib.CDC_E_NOSPACE:
+        rows = (_lib.cdc_packfile_row * need.value)()
+        rc = L.cdc_packfile_index(data, len(data), ctypes.byref(f), rows, need.value, ctypes.byref(need))
+    check(rc, "cdc_packfile_index")
+    footer = dict(version=int(f.version), timestamp=int(f.timestamp), count=int(f.count),
+                  index_offset=int(f.index_offset), index_checksum=bytes(f.index_checksum))
+    return footer, [(int(r.type), bytes(r.checksum), int(r.offset), int(r.length)) for r in (rows or [])]
+
+
+def _u64(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1))
+
+
+def assemble_device(src, segments, dst, device=None, stream=None):
+    """cdc_assemble_device over torch uint8 tensors: dst[dst_off:dst_off + len] =
+    src[src_off:src_off + len] for every (src_off, len, dst_off) of `segments`
+    (destinations sorted and disjoint).  Asynchronous on the current stream."""
+    import torch
+    ensure_init()
+    seg = np.asarray(segments, dtype=np.uint64).reshape(-1, 3)
+    so, ln, do = _u64(seg[:, 0]), _u64(seg[:, 1]), _u64(seg[:, 2])
+    dev = dst.device.index if device is None else device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    p64 = ctypes.POINTER(ctypes.c_uint64)
+    rc = lib().cdc_assemble_device(int(dev), ctypes.c_void_p(src.data_ptr()), src.numel(), so.ctypes.data_as(p64),
+                                   ln.ctypes.data_as(p64), do.ctypes.data_as(p64), len(so),
+                                   ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(s.cuda_stream))
+    check(rc, "cdc_assemble_device")
+
+
+class RestoreSession:
+    """A native restore context (cdc_restore_new): Decode's configuration
+    (compression "LZ4" or None, the 32-byte key or None), the registered
+    packfiles and their locator, with its streams and buffers kept across
+    runs.  add_packfile() takes a serialised packfile (bytes) or a path;
+    run() restores a list of objects."""
+
+    def __init__(self, key=None, compression="LZ4", verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES,
+                 device=0):
+        if compression not in (None, "LZ4"):
+            raise ValueError(f"unsupported compression {compression!r}")
+        self._h = None
+        self._keep = []  # packfile bytes the context reads from until it is freed
+        keybuf = None
+        if key is not None:
+            key = bytes(key)
+            if len(key) != 32:
+                raise ValueError("the repository key is 32 bytes (AES-256)")
+            keybuf = ctypes.create_string_buffer(key, 32)
+        ensure_init()
+        o = _lib.cdc_restore_opts()
+        lib().cdc_restore_default_opts(ctypes.byref(o))
+        o.compress = 1 if compression == "LZ4" else 0
+        o.key = ctypes.cast(keybuf, ctypes.c_void_p) if keybuf is not None else None
+        o.verify, o.writers, o.batch_bytes = int(bool(verify)), int(writers), int(batch_bytes)
+        h = ctypes.c_void_p()
+        check(lib().cdc_restore_new(int(device), ctypes.byref(o), ctypes.byref(h)), "cdc_restore_new")
+        self._h = h
+
+    def add_packfile(self, packfile):
+        """Register a packfile: bytes (kept alive by the session) or a path."""
+        if not self._h:
+            raise ValueError("session closed")
+        if isinstance(packfile, (str, os.PathLike)):
+            check(lib().cdc_restore_add_packfile_path(self._h, os.fsencode(packfile)), "cdc_restore_add_packfile_path")
+            return
+        buf = bytes(packfile)
+        check(lib().cdc_restore_add_packfile(self._h, buf, len(buf)), "cdc_restore_add_packfile")
+        self._keep.append(buf)
+
+    def run(self, objects, dests=None):
+        """Restore the objects (snapshot.Object, as backup_files returns them;
+        only Chunks' Checksum and Length are read).  dests: one destination
+        path per object, or None: the bytes come back.  Returns (contents,
+        statuses, stats): contents[i] the file's bytes (None for a failed
+        file, and for every file when dests are given), statuses[i] 0 or the
+        file's CDC_E_* code, stats the fields of cdc_restore_stats."""
+        if not self._h:
+            raise ValueError("session closed")
+        n = len(objects)
+        if dests is not None and len(dests) != n:
+            raise ValueError("one destination per object")
+        files = (_lib.cdc_restore_file * max(n, 1))()
+        keep = []
+        for i, obj in enumerate(objects):
+            chunks = obj.Chunks
+            sums = b"".join(bytes(c.Checksum) for c in chunks)
+            if len(sums) != 32 * len(chunks):
+                raise ValueError("a chunk checksum is 32 bytes (SHA-256)")
+            lens = np.array([int(c.Length) for c in chunks], dtype=np.uint32)
+            sbuf = ctypes.create_string_buffer(sums, max(len(sums), 1))
+            keep.append((sbuf, lens))
+            files[i].path = os.fsencode(dests[i]) if dests is not None else None
+            files[i].nchunks = len(chunks)
+            files[i].checksums = ctypes.cast(sbuf, ctypes.c_void_p)
+            files[i].lengths = lens.ctypes.data if lens.size else None
+        statuses = [None] * n
+        parts = [[] for _ in range(n)]
+        errors = []
+
+        def on_file(_ctx, rp):
+            try:
+                r = rp.contents
+                i = int(r.index)
+                statuses[i] = int(r.status)
+                if r.status == 0 and dests is None:
+                    parts[i].append(ctypes.string_at(r.data, int(r.data_len)) if r.data_len else b"")
+            except Exception as e:  # noqa: BLE001 - re-raised after the call
+                errors.append(e)
+
+        cb = _lib.RESTORE_FILE_FN(on_file)
+        st = _lib.cdc_restore_stats()
+        rc = lib().cdc_restore_files(self._h, files, n, cb, None, ctypes.byref(st))
+        check(rc, "cdc_restore_files")
+        if errors:
+            raise errors[0]
+        contents = [b"".join(parts[i]) if dests is None and statuses[i] == 0 else None for i in range(n)]
+        stats = {name: getattr(st, name) for name, _ in _lib.cdc_restore_stats._fields_}
+        return contents, statuses, stats
+
+    def close(self):
+        if self._h:
+            lib().cdc_restore_free(self._h)
+            self._h = None
+            self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def restore_files(objects, packfiles, dests=None, key=None, compression="LZ4", verify=True, writers=8,
+                  batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+    """One restore through the native pipeline (a RestoreSession for this call
+    only): packfiles is a list of serialised packfiles (bytes) and/or paths.
+    Returns (contents, statuses, stats) as RestoreSession.run."""
+    with RestoreSession(key, compression, verify, writers, batch_bytes, device) as s:
+        for p in packfiles:
+            s.add_packfile(p)
+        return s.run(objects, dests)
+
+
+__all__ = ["packfile_index", "assemble_device", "RestoreSession", "restore_files", "DEFAULT_BATCH_BYTES"]

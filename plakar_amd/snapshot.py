@@ -444,4 +444,7 @@ def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", kn
         return s.run(paths, keep_packfiles)
 
 
-__all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files"]
+from .restore import RestoreSession, restore_files  # noqa: E402 - the read path, next to backup_files
+
+__all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
+           "RestoreSession", "restore_files"]
