@@ -148,7 +148,8 @@ void cdc_collector_free(cdc_collector *c);
 /* ---- Encode: LZ4 frame, then the AES-256-GCM stream ----------------------------
  * (*Repository).Encode (repository/repository.go:212-236) of n blobs that sit
  * in device memory at d_base + offsets[i], lens[i] bytes each:
- *   compress != 0: the LZ4 frame of compression.DeflateLZ4Stream
+ *   compress != 0 (a flag, not Decode's selector: every non-zero value means
+ *     LZ4, GZIP is not written): the LZ4 frame of compression.DeflateLZ4Stream
  *     (compression/compression.go:94-106; pierrec/lz4/v4 writer defaults:
  *     4-MiB independent blocks, content checksum; a block that does not
  *     shrink is stored);
@@ -169,7 +170,7 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
 /* Upper bound of one blob's encoding (for out_cap). */
 uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
 
-/* ---- Decode: open the AES-256-GCM stream, then inflate the LZ4 frame -----------
+/* ---- Decode: open the AES-256-GCM stream, then inflate (LZ4 or GZIP) -------------
  * (*Repository).Decode (repository/repository.go:186-210) of n encoded blobs
  * that sit in device memory at d_in + offsets[i], lens[i] bytes each:
  *   key != NULL (32 bytes, host memory): encryption.DecryptStream
@@ -180,12 +181,31 @@ uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
  *     trailing record under 28 is CDC_E_CORRUPT (the reference takes exactly
  *     12 trailing bytes for a clean end; no writer produces them and they are
  *     rejected here), a tag that does not verify CDC_E_AUTH.
- *   compressed != 0: compression.InflateLZ4Stream (compression/compression.go:
- *     148-160; empty input is an empty blob, compression.go:108-116): one LZ4
- *     frame of independent blocks, any block maximum, with or without block
+ *   compressed == CDC_COMPRESS_LZ4 (1; or any value but 0 and 2):
+ *     compression.InflateLZ4Stream (compression/compression.go:148-160;
+ *     empty input is an empty blob, compression.go:108-116): one LZ4 frame
+ *     of independent blocks, any block maximum, with or without block
  *     checksums, content size and content checksum, all verified
  *     (CDC_E_CORRUPT).  Linked blocks, a dictionary ID, skippable and legacy
  *     frames are CDC_E_UNSUPPORTED (pierrec/lz4 v4's writer makes none).
+ *   compressed == CDC_COMPRESS_GZIP (2): compression.InflateGzipStream
+ *     (compression/compression.go:32-55, 108-146, over Go's compress/gzip;
+ *     the other algorithm a repository's configuration may name): one gzip
+ *     member (RFC 1952) whose
+ *     body is DEFLATE (RFC 1951: stored, fixed and dynamic blocks), the
+ *     optional header fields skipped (FHCRC verified), CRC-32 and ISIZE
+ *     verified.  A malformed header, block, code set, distance or trailer is
+ *     CDC_E_CORRUPT (plakar_amd/csrc/inflate_walk.h has the list); so is an
+ *     ISIZE of more than 1032 bytes per body byte, which DEFLATE cannot
+ *     reach, so a few bytes cannot make the call ask for gigabytes.  A second
+ *     member after the first and a stream of 2 GiB or more are
+ *     CDC_E_UNSUPPORTED (Go's writer makes neither).  Empty input is an empty
+ *     blob.  There is no preset dictionary.
+ *   The selector: CDC_COMPRESS_NONE (0), CDC_COMPRESS_LZ4 (1), CDC_COMPRESS_GZIP
+ *     (2).  Any other non-zero value means LZ4, as it did before GZIP existed.
+ *     cdc_decode_device, cdc_check_device and cdc_restore_opts.compress take
+ *     it.  Encode and the backup pipeline do not: their `compress` is a flag
+ *     whose non-zero value means LZ4 (writing GZIP is not built).
  *   compressed == 0 and key == NULL: a plain copy.
  * Blob i's plaintext lands at d_out + out_offsets[i] (host array of n + 1,
  * out_offsets[n] = total), blobs packed without padding, so (out_offsets[i],
@@ -196,13 +216,17 @@ uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
  * first: when they exceed out_cap it returns CDC_E_NOSPACE with
  * out_offsets[n] the capacity needed and nothing written (d_out may be NULL
  * when out_cap is 0).  d_out[out_offsets[n], out_cap) is scratch for the
- * call: a frame whose content checksum fails is found out only after it was
- * written, the blobs after it are then moved down over it, and the bytes
- * between the final out_offsets[n] and the total planned before that failure
- * are left overwritten.  Keep nothing of your own behind out_offsets[n] in
+ * call: an LZ4 frame whose content checksum fails, and a gzip member with any
+ * fault in its body or trailer, is found out only after it was (partly)
+ * written into its planned range, the blobs after it are then moved down
+ * over it, and the bytes between the final out_offsets[n] and the total
+ * planned before that failure are left overwritten.  Keep nothing of your own behind out_offsets[n] in
  * the same buffer.  Synchronous on `stream`. */
+#define CDC_COMPRESS_NONE 0
+#define CDC_COMPRESS_LZ4  1
+#define CDC_COMPRESS_GZIP 2
 #define CDC_E_AUTH     (-12) /* a GCM tag did not verify (sealed subkey or a data record) */
-#define CDC_E_CORRUPT  (-13) /* malformed stream: short record, bad LZ4 frame/block, checksum or content-size mismatch */
+#define CDC_E_CORRUPT  (-13) /* malformed stream: short record, bad LZ4 frame/block or gzip member, checksum or size mismatch */
 #define CDC_E_MISMATCH (-14) /* cdc_check_device: decoded fine, SHA-256 differs from the expected checksum */
 int cdc_decode_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                       int compressed, const uint8_t *key, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
@@ -285,7 +309,7 @@ void cdc_packer_free(cdc_packer *p);
 typedef struct cdc_backup_opts {
     cdc_opts chunking;
     uint32_t packfile_max;
-    int compress;
+    int compress;             /* a flag: non-zero means LZ4 (not the Decode selector: GZIP is not written) */
     const uint8_t *key;       /* 32-byte repository key, or NULL: no encryption */
     int packers;              /* packer threads (0: 8, NumCPU in the reference) */
     int readers;              /* reader threads (0: 8) */
@@ -422,7 +446,7 @@ int cdc_debug_set_assemble_policy(int policy);
  * repository.go:449-466), three streams and its pinned / device buffers kept
  * across runs (grown on demand).  One cdc_restore_files at a time per context. */
 typedef struct cdc_restore_opts {
-    int compress;
+    int compress;          /* CDC_COMPRESS_NONE, _LZ4 or _GZIP, as cdc_decode_device's `compressed` */
     const uint8_t *key;    /* 32-byte repository key, or NULL: not encrypted */
     int verify;            /* 0: off; otherwise every decoded blob's SHA-256 is compared with its checksum */
     int writers;          /* reader and writer threads (0: 8) */

@@ -33,6 +33,19 @@ CDC_E_CORRUPT = -13
 CDC_E_MISMATCH = -14
 CDC_E_NOTFOUND = -15
 
+# the compression selector of cdc_decode_device, cdc_check_device and cdc_restore_opts.compress
+CDC_COMPRESS_NONE = 0
+CDC_COMPRESS_LZ4 = 1
+CDC_COMPRESS_GZIP = 2
+
+
+def compress_code(compression):
+    """The selector for a repository's compression name ("LZ4", "GZIP" or None)."""
+    try:
+        return {None: CDC_COMPRESS_NONE, "LZ4": CDC_COMPRESS_LZ4, "GZIP": CDC_COMPRESS_GZIP}[compression]
+    except (KeyError, TypeError):
+        raise ValueError(f"unsupported compression {compression!r} (the read path implements LZ4 and GZIP)") from None
+
 
 class cdc_opts(ctypes.Structure):
     _fields_ = [("min_size", ctypes.c_uint32), ("normal_size", ctypes.c_uint32),

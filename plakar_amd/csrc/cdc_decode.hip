@@ -29,6 +29,15 @@
 //                 plan: moves the later blobs down so that the failed one
 //                 contributes no bytes
 //   k_dec_copy    neither compressed nor encrypted: the blob itself
+// With compressed == CDC_COMPRESS_GZIP (compression.InflateGzipStream, compression/
+// compression.go:130-146) two kernels stand in the place of the LZ4 ones:
+//   k_gz_size     one wave per blob: the member header, the trailer's place,
+//                 ISIZE as the claimed size, the 1032 : 1 ceiling.  It does not
+//                 inflate: the claim is a plan
+//   k_gz_emit     one wave per blob: inflates into the planned range (at most
+//                 the claim: inflate_walk.h bounds every literal and match),
+//                 then CRC-32 and ISIZE against the output.  Every failure
+//                 here is late (kFlagLate): k_dec_compact closes the gap
 //
 // No block table is kept: both LZ4 passes walk the frame from its header, so
 // a frame of very many short blocks needs no memory of its own (it only runs
@@ -54,6 +63,7 @@
 
 #include "cdc_crypto_dev.h"
 #include "cdc_internal.h"
+#include "inflate_walk.h"
 #include "lz4_walk.h"
 
 namespace dec {
@@ -78,7 +88,7 @@ struct DBlob {       // planned on the host from the lengths
 
 struct DBatch {
     const uint8_t *in;
-    uint32_t n, compressed, encrypted, nrecs;
+    uint32_t n, compressed, encrypted, nrecs;  // compressed: 0, 1 (LZ4) or 2 (GZIP)
     const DBlob *blobs;
     const uint8_t *key;   // repository key (32 B, device)
     uint8_t *frames;
@@ -86,7 +96,7 @@ struct DBatch {
     uint64_t out_cap;
     BlobKey *keys;        // per blob
     int32_t *status;      // per blob
-    uint64_t *dsize;      // per blob: decoded bytes (k_lz4_size)
+    uint64_t *dsize;      // per blob: decoded bytes (k_lz4_size), or the claim (k_gz_size)
     uint64_t *out_off;    // n + 1
     uint32_t *flags;      // see kFlag*
 };
@@ -543,6 +553,152 @@ __global__ __launch_bounds__(kFrameWaves * 64) void k_lz4_emit(const DBatch B)
 }
 
 // ---------------------------------------------------------------------------
+// f. The gzip member (compressed == CDC_COMPRESS_GZIP), one wave per blob.
+// inflate_walk.h decides every bound; what is here is where the bytes go.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kGzWaves = 4;
+
+__device__ __forceinline__ int32_t gz_status(int st)
+{
+    return st == infw::kOk ? CDC_OK : st == infw::kUnsupported ? CDC_E_UNSUPPORTED : CDC_E_CORRUPT;
+}
+
+// The wave's lanes share a table build; LDS traffic of one wave stays in
+// order, so the barrier only has to hold the compiler.
+struct WavePar {
+    uint32_t lane;
+    static constexpr uint32_t nl = 64;
+    __device__ __forceinline__ void sync()
+    {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+};
+
+// Literals wait one per lane and leave as one store; a match gathers from the
+// output in global memory (flushed literals included) and waits for the wave's
+// own stores only when it reaches into bytes stored since the last wait.
+struct GzSink {
+    uint8_t *dst;
+    const uint8_t *src;
+    uint32_t lane, pend, fbase, published, litv;
+    __device__ __forceinline__ void flush()
+    {
+        if (pend) {
+            if (lane < pend) dst[fbase + lane] = uint8_t(litv);
+            pend = 0;
+        }
+    }
+    __device__ __forceinline__ void lit(uint32_t o, uint32_t b)
+    {
+        if (pend == 0) fbase = o;
+        litv = lane == pend ? b : litv;  // a select at a uniform index: lane `pend` keeps the byte
+        if (++pend == 64) flush();
+    }
+    __device__ __forceinline__ void match(uint32_t o, uint32_t dist, uint32_t len)
+    {
+        flush();
+        if (o - dist + min(dist, len) > published) {
+            wave_publish();
+            published = o;
+        }
+        for (uint32_t i = lane; i < len; i += 64) dst[o + i] = dst[lz4w::match_src(o, dist, len, i)];
+    }
+    __device__ __forceinline__ void stored(uint32_t o, uint32_t s, uint32_t len)
+    {
+        flush();
+        copy_exact(dst + o, src + s, len, lane, 64);
+    }
+};
+
+// CRC-32 of p[0, n) by one wave: every lane runs the byte table (T, in LDS)
+// over its slice, and the 64 registers fold in six steps, the left half of
+// each pair multiplied by x^(8 * the right half's bytes) mod P.
+__device__ uint32_t wave_crc32(const uint8_t *p, uint64_t n, uint32_t lane, const uint32_t *T)
+{
+    if (n == 0) return 0;
+    uint64_t lo, hi;
+    uint32_t reg;
+    infw::crc_slice(n, lane, lo, hi, reg);
+    uint64_t i = lo;
+    for (; i + 16 <= hi; i += 16) {
+        uint32_t w[4];
+        __builtin_memcpy(w, p + i, 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            reg ^= w[q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) reg = T[reg & 255u] ^ (reg >> 8);
+        }
+    }
+    for (; i < hi; ++i) reg = T[(reg ^ p[i]) & 255u] ^ (reg >> 8);
+    uint32_t M = infw::crc_xpow(8u * infw::crc_slice_len(n));
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t right = __shfl_down(reg, d);
+        reg = infw::crc_mul(reg, M) ^ right;
+        M = infw::crc_mul(M, M);
+    }
+    return uint32_t(__builtin_amdgcn_readfirstlane(int(reg))) ^ 0xFFFFFFFFu;
+}
+
+// Sizing does not inflate: the header, the trailer's place, ISIZE as the
+// claim, and the 1032 : 1 ceiling.  Emit proves the claim.
+__global__ __launch_bounds__(kGzWaves * 64) void k_gz_size(const DBatch B)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t b = blockIdx.x * kGzWaves + (threadIdx.x >> 6);
+    if (b >= B.n) return;
+    uint32_t claim = 0;
+    if (B.status[b] == 0) {
+        const DBlob D = B.blobs[b];
+        const uint32_t n = uint32_t(min<uint64_t>(D.flen, infw::kMaxStream));
+        WaveRd rd{stream_ptr(B, D), n, lane, n, 0u};
+        uint32_t hlen;
+        const int st = infw::member_claim(rd, D.flen, hlen, claim);
+        if (st != infw::kOk) {
+            claim = 0;
+            if (lane == 0) B.status[b] = gz_status(st);
+        }
+    }
+    if (lane == 0) B.dsize[b] = claim;
+}
+
+__global__ __launch_bounds__(kGzWaves * 64) void k_gz_emit(const DBatch B)
+{
+    __shared__ infw::Tables s_fixed;
+    __shared__ infw::Tables s_dyn[kGzWaves];
+    __shared__ uint32_t s_crc[256];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    WavePar par{lane};
+    if (wv == 0) infw::build_fixed(par, s_fixed);
+    for (uint32_t i = threadIdx.x; i < 256; i += kGzWaves * 64) s_crc[i] = infw::crc_bits(0, i);
+    __syncthreads();
+    const uint32_t b = blockIdx.x * kGzWaves + wv;
+    if (b >= B.n || B.flags[kFlagNoSpace] || B.status[b]) return;
+    const DBlob D = B.blobs[b];
+    if (D.flen == 0 || D.flen > infw::kMaxStream) return;  // the empty blob (sizing refused the other)
+    const uint32_t n = uint32_t(D.flen), claim = uint32_t(B.dsize[b]);
+    const uint8_t *f = stream_ptr(B, D);
+    uint8_t *dst = B.out + B.out_off[b];
+    WaveRd rd{f, n, lane, n, 0u};
+    uint32_t hlen = 0, opos = 0, end = 0;
+    int st = infw::member_header(rd, n, hlen);  // again: nothing is taken from the sizing pass but the claim
+    if (st == infw::kOk) {
+        GzSink sink{dst, f, lane, 0u, 0u, 0u, 0u};
+        st = infw::inflate_body(rd, n, hlen, sink, claim, s_dyn[wv], s_fixed, par, opos, end);
+    }
+    if (st == infw::kOk) {
+        wave_publish();
+        st = infw::member_trailer(rd, n, end, opos, wave_crc32(dst, opos, lane, s_crc));
+    }
+    if (st == infw::kOk && opos != claim) st = infw::kCorrupt;
+    if (st != infw::kOk && lane == 0) {
+        B.status[b] = gz_status(st);
+        B.flags[kFlagLate] = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // The plan: out_off = exclusive scan of the sizes of the blobs that decoded.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPlanThreads = 1024;
@@ -833,7 +989,7 @@ extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *o
     DBatch B{};
     B.in = static_cast<const uint8_t *>(d_in);
     B.n = n;
-    B.compressed = compressed ? 1u : 0u;
+    B.compressed = compressed == CDC_COMPRESS_GZIP ? 2u : compressed ? 1u : 0u;
     B.encrypted = encrypt ? 1u : 0u;
     B.nrecs = uint32_t(nrecs);
     B.blobs = reinterpret_cast<const DBlob *>(ws + o_blobs);
@@ -858,10 +1014,14 @@ extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *o
                 hipLaunchKernelGGL(k_rec_open, dim3(open_wgs), dim3(kGcmWaves * 64), 0, s, B,
                                    compressed ? (kOpenHash | kOpenCtr) : kOpenHash);
         }
-        if (compressed) hipLaunchKernelGGL(k_lz4_size, frame_grid, dim3(kFrameWaves * 64), 0, s, B);
+        const bool gzip = B.compressed == 2u;
+        const dim3 gz_grid((n + kGzWaves - 1) / kGzWaves);
+        if (gzip) hipLaunchKernelGGL(k_gz_size, gz_grid, dim3(kGzWaves * 64), 0, s, B);
+        else if (compressed) hipLaunchKernelGGL(k_lz4_size, frame_grid, dim3(kFrameWaves * 64), 0, s, B);
         hipLaunchKernelGGL(k_dec_plan, dim3(1), dim3(kPlanThreads), 0, s, B);
         if (compressed) {
-            hipLaunchKernelGGL(k_lz4_emit, frame_grid, dim3(kFrameWaves * 64), 0, s, B);
+            if (gzip) hipLaunchKernelGGL(k_gz_emit, gz_grid, dim3(kGzWaves * 64), 0, s, B);
+            else hipLaunchKernelGGL(k_lz4_emit, frame_grid, dim3(kFrameWaves * 64), 0, s, B);
             hipLaunchKernelGGL(k_dec_compact, dim3(1), dim3(256), 0, s, B);
         } else if (encrypt) {
             if (nrecs)

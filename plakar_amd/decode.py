@@ -1,9 +1,9 @@
 """Decode on the device: plakar's (*Repository).Decode (repository/repository.go:
 186-210) for a batch of blobs -- encryption.DecryptStream (encryption/
 symmetric.go:165-243) when a key is configured, then compression.
-InflateLZ4Stream (compression/compression.go:148-160) -- and the blob check of
-snapshot/check.go:83-98 (decode, SHA-256, compare) with the plaintext staying
-on the device.  Every call goes through the C ABI (cdc_decode_device,
+InflateLZ4Stream or InflateGzipStream (compression/compression.go:130-160) --
+and the blob check of snapshot/check.go:83-98 (decode, SHA-256, compare) with
+the plaintext staying on the device.  Every call goes through the C ABI (cdc_decode_device,
 cdc_check_device)."""
 import ctypes
 
@@ -33,6 +33,13 @@ def _u64(a, n):
     return a
 
 
+def _sel(compressed):
+    """The C selector: False / True (the LZ4 frame) or the string "GZIP"."""
+    if isinstance(compressed, str):
+        return _lib.compress_code(compressed)
+    return int(bool(compressed))
+
+
 def _ptr(a, ctype):
     return a.ctypes.data_as(ctypes.POINTER(ctype)) if a.size else (ctype * 1)()
 
@@ -43,7 +50,8 @@ def decode_device(base, offsets, lens, out, key=None, compressed=True, device=0,
     (out_offsets, status), n + 1 int64 offsets and n int32 codes.  Blob i's
     plaintext is out[out_offsets[i]:out_offsets[i + 1]]; a failed blob has
     status[i] != 0 and no bytes.  Raises CdcError(CDC_E_NOSPACE) when `out` is
-    too small (.needed: the bytes to retry with)."""
+    too small (.needed: the bytes to retry with).  `compressed`: False, True
+    (an LZ4 frame) or "GZIP" (a gzip member)."""
     import torch
     ensure_init()
     n = len(lens)
@@ -52,7 +60,7 @@ def decode_device(base, offsets, lens, out, key=None, compressed=True, device=0,
     st_a = np.zeros(n, dtype=np.int32)
     s = stream if stream is not None else torch.cuda.current_stream(device)
     rc = lib().cdc_decode_device(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs_a, ctypes.c_uint64),
-                                 _ptr(lens_a, ctypes.c_uint64), n, int(bool(compressed)), _key(key),
+                                 _ptr(lens_a, ctypes.c_uint64), n, _sel(compressed), _key(key),
                                  ctypes.c_void_p(out.data_ptr()), out.numel(), _ptr(oo_a, ctypes.c_uint64),
                                  _ptr(st_a, ctypes.c_int32), ctypes.c_void_p(s.cuda_stream))
     if rc < 0:
@@ -76,7 +84,8 @@ def _upload(blobs, device):
 
 def decode_blobs(blobs, key=None, compressed=True, device=0):
     """Decode host byte buffers: a list with each blob's plaintext (bytes), or
-    a DecodeError in the place of a blob that did not decode."""
+    a DecodeError in the place of a blob that did not decode.  `compressed`
+    as for decode_device."""
     import torch
     if not len(blobs):
         return []
@@ -119,7 +128,7 @@ def check_blobs(blobs, checksums, key=None, compressed=True, device=0):
     while True:
         scratch = torch.empty(cap, dtype=torch.uint8, device=base.device)
         rc = lib().cdc_check_device(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs, ctypes.c_uint64),
-                                    _ptr(lens, ctypes.c_uint64), n, int(bool(compressed)), _key(key), want,
+                                    _ptr(lens, ctypes.c_uint64), n, _sel(compressed), _key(key), want,
                                     ctypes.c_void_p(scratch.data_ptr()), cap, ctypes.byref(needed),
                                     _ptr(st_a, ctypes.c_int32), ctypes.c_void_p(s.cuda_stream))
         if rc == _lib.CDC_E_NOSPACE and needed.value > cap:
@@ -131,16 +140,15 @@ def check_blobs(blobs, checksums, key=None, compressed=True, device=0):
 
 class DeviceDecoder:
     """(*Repository).Decode with the repository's configuration, the
-    counterpart of DeviceEncoder: compression "LZ4" or None, and the
+    counterpart of DeviceEncoder: compression "LZ4", "GZIP" or None, and the
     encryption key (None: not encrypted).  `decode_many` decodes a batch in
     one device call, `check_many` verifies a batch against its checksums;
     calling the object decodes one blob, like Decode (and raises its error)."""
 
     def __init__(self, key=None, compression="LZ4", device=0):
-        if compression not in (None, "LZ4"):
-            raise ValueError(f"unsupported compression {compression!r} (the device path implements LZ4)")
+        code = _lib.compress_code(compression)
         self.key = _key(key)
-        self.compressed = compression == "LZ4"
+        self.compressed = "GZIP" if code == _lib.CDC_COMPRESS_GZIP else bool(code)
         self.device = device
 
     def decode_many(self, blobs):

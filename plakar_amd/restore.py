@@ -62,15 +62,14 @@ def assemble_device(src, segments, dst, device=None, stream=None):
 
 class RestoreSession:
     """A native restore context (cdc_restore_new): Decode's configuration
-    (compression "LZ4" or None, the 32-byte key or None), the registered
+    (compression "LZ4", "GZIP" or None, the 32-byte key or None), the registered
     packfiles and their locator, with its streams and buffers kept across
     runs.  add_packfile() takes a serialised packfile (bytes) or a path;
     run() restores a list of objects."""
 
     def __init__(self, key=None, compression="LZ4", verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES,
                  device=0):
-        if compression not in (None, "LZ4"):
-            raise ValueError(f"unsupported compression {compression!r}")
+        code = _lib.compress_code(compression)
         self._h = None
         self._keep = []  # packfile bytes the context reads from until it is freed
         keybuf = None
@@ -82,7 +81,7 @@ class RestoreSession:
         ensure_init()
         o = _lib.cdc_restore_opts()
         lib().cdc_restore_default_opts(ctypes.byref(o))
-        o.compress = 1 if compression == "LZ4" else 0
+        o.compress = code
         o.key = ctypes.cast(keybuf, ctypes.c_void_p) if keybuf is not None else None
         o.verify, o.writers, o.batch_bytes = int(bool(verify)), int(writers), int(batch_bytes)
         h = ctypes.c_void_p()
