@@ -145,14 +145,25 @@ int cdc_collector_chunk(cdc_collector *c, const void *data, uint64_t len, cdc_cu
 int cdc_collector_stats(cdc_collector *c, uint64_t *requests, uint64_t *batches);
 void cdc_collector_free(cdc_collector *c);
 
-/* ---- Encode: LZ4 frame, then the AES-256-GCM stream ----------------------------
+/* ---- Encode: LZ4 frame or gzip member, then the AES-256-GCM stream --------------
  * (*Repository).Encode (repository/repository.go:212-236) of n blobs that sit
  * in device memory at d_base + offsets[i], lens[i] bytes each:
- *   compress != 0 (a flag, not Decode's selector: every non-zero value means
- *     LZ4, GZIP is not written): the LZ4 frame of compression.DeflateLZ4Stream
+ *   compress: Decode's selector (CDC_COMPRESS_NONE, _LZ4, _GZIP below; every
+ *     other non-zero value means LZ4).
+ *   compress == CDC_COMPRESS_LZ4: the LZ4 frame of compression.DeflateLZ4Stream
  *     (compression/compression.go:94-106; pierrec/lz4/v4 writer defaults:
  *     4-MiB independent blocks, content checksum; a block that does not
  *     shrink is stored);
+ *   compress == CDC_COMPRESS_GZIP: the gzip member of
+ *     compression.DeflateGzipStream (compression.go:78-92): the ten header
+ *     bytes Go's gzip.NewWriter writes (1f 8b 08, no flags, MTIME 0, XFL 0,
+ *     OS 255), one DEFLATE stream, CRC-32 and ISIZE, nothing after them.  The
+ *     DEFLATE bytes are not Go's (compress/flate level 6): each 32-KiB span
+ *     is one block, stored, fixed or dynamic Huffman, whichever is smallest,
+ *     with matches inside 8-KiB segments; any inflater reads them.  An empty
+ *     blob is an empty stream (compression.go:58-62) under either name.  A
+ *     blob of 2 GiB or more is CDC_E_UNSUPPORTED (ISIZE is 32 bits and Decode
+ *     refuses such a stream), reported before the device is touched;
  *   key != NULL (32 bytes, host memory): then encryption.EncryptStream
  *     (encryption/symmetric.go:72-163): subkey nonce (12) || Seal(key,
  *     subkey nonce, subkey) (48) || per 64-KiB piece k of the stream: nonce
@@ -162,12 +173,15 @@ void cdc_collector_free(cdc_collector *c);
  *     last four bytes XOR k (big-endian).
  * Blob i's encoding lands at d_out + out_offsets[i] (device memory; host
  * array of n + 1 offsets, out_offsets[n] = total).  Returns CDC_E_NOSPACE
- * when out_cap is smaller than out_offsets[n].  Synchronous on `stream`. */
+ * when out_cap is smaller than out_offsets[n], CDC_E_INVALID for a NULL
+ * argument or a device outside 0..63.  Synchronous on `stream`. */
 int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                       int compress, const uint8_t *key, const uint8_t *random, uint8_t *d_out, uint64_t out_cap,
                       uint64_t *out_offsets, void *stream);
 
-/* Upper bound of one blob's encoding (for out_cap). */
+/* Upper bound of one blob's encoding (for out_cap); `compress` is the selector.
+ * GZIP: len + 18 + 5 * (ceil(len / 32768) + 1) before encryption (a span is
+ * coded only when that is no larger than storing it). */
 uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
 
 /* ---- Decode: open the AES-256-GCM stream, then inflate (LZ4 or GZIP) -------------
@@ -203,9 +217,8 @@ uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
  *     blob.  There is no preset dictionary.
  *   The selector: CDC_COMPRESS_NONE (0), CDC_COMPRESS_LZ4 (1), CDC_COMPRESS_GZIP
  *     (2).  Any other non-zero value means LZ4, as it did before GZIP existed.
- *     cdc_decode_device, cdc_check_device and cdc_restore_opts.compress take
- *     it.  Encode and the backup pipeline do not: their `compress` is a flag
- *     whose non-zero value means LZ4 (writing GZIP is not built).
+ *     cdc_decode_device, cdc_check_device, cdc_restore_opts.compress,
+ *     cdc_encode_device, cdc_encode_bound and cdc_backup_opts.compress take it.
  *   compressed == 0 and key == NULL: a plain copy.
  * Blob i's plaintext lands at d_out + out_offsets[i] (host array of n + 1,
  * out_offsets[n] = total), blobs packed without padding, so (out_offsets[i],
@@ -276,7 +289,7 @@ void cdc_packer_free(cdc_packer *p);
  * over batches of whole files (at most batch_bytes each, 0: 256 MiB): reader
  * threads read each file into a pinned arena and SHA-256 it there (the
  * object checksum); the device cuts, digests (SHA-256 + byte histogram per
- * chunk) and Encodes the new chunks (LZ4 when compress, then AES-256-GCM
+ * chunk) and Encodes the new chunks (LZ4 or GZIP as compress says, then AES-256-GCM
  * when key != NULL; a chunk whose digest is in `known` (sorted, 32 B each:
  * BlobExists) or was already seen in this run is not stored again); packer
  * threads append the blobs to their own packfiles and hand each one, at
@@ -309,7 +322,7 @@ void cdc_packer_free(cdc_packer *p);
 typedef struct cdc_backup_opts {
     cdc_opts chunking;
     uint32_t packfile_max;
-    int compress;             /* a flag: non-zero means LZ4 (not the Decode selector: GZIP is not written) */
+    int compress;             /* CDC_COMPRESS_NONE, _LZ4 or _GZIP, as cdc_encode_device's `compress` */
     const uint8_t *key;       /* 32-byte repository key, or NULL: no encryption */
     int packers;              /* packer threads (0: 8, NumCPU in the reference) */
     int readers;              /* reader threads (0: 8) */

@@ -33,7 +33,8 @@ CDC_E_CORRUPT = -13
 CDC_E_MISMATCH = -14
 CDC_E_NOTFOUND = -15
 
-# the compression selector of cdc_decode_device, cdc_check_device and cdc_restore_opts.compress
+# the compression selector of cdc_encode_device, cdc_decode_device, cdc_check_device and the
+# backup and restore options' `compress`
 CDC_COMPRESS_NONE = 0
 CDC_COMPRESS_LZ4 = 1
 CDC_COMPRESS_GZIP = 2
@@ -44,7 +45,7 @@ def compress_code(compression):
     try:
         return {None: CDC_COMPRESS_NONE, "LZ4": CDC_COMPRESS_LZ4, "GZIP": CDC_COMPRESS_GZIP}[compression]
     except (KeyError, TypeError):
-        raise ValueError(f"unsupported compression {compression!r} (the read path implements LZ4 and GZIP)") from None
+        raise ValueError(f"unsupported compression {compression!r} (LZ4 and GZIP are implemented)") from None
 
 
 class cdc_opts(ctypes.Structure):

@@ -37,6 +37,19 @@
 // caller (the host fills them from the OS CSPRNG), as crypto/rand does in
 // the reference; piece k of a blob uses the blob's data nonce with its last
 // four bytes XOR k (big-endian), unique per subkey.
+//
+// compress == CDC_COMPRESS_GZIP writes the gzip member of
+// compression.DeflateGzipStream (compression/compression.go:78-92) instead of
+// the LZ4 frame: k_lz4_seq's records feed a DEFLATE writer (deflate_enc.h),
+//   k_dfl_size    one workgroup per 32-KiB span (four segments): histograms,
+//                 code lengths, the dynamic header, the block's size as fixed
+//                 and as dynamic Huffman, and the span's CRC-32
+//   k_enc_plan    also walks each blob's spans: stored, fixed or dynamic by
+//                 exact bit count at the running bit position
+//   k_dfl_emit    one workgroup per span: its block, packed in LDS
+//   k_gz_fin      one wave per blob: header, the bytes two spans share, the
+//                 CRC-32 combined from the spans', ISIZE
+// in the place of k_xxh32, k_lz4_size, k_lz4_emit and k_frame_fin.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +59,8 @@
 
 #include "cdc_internal.h"
 #include "cdc_crypto_dev.h"
+#include "deflate_enc.h"
+#include "inflate_walk.h"
 
 namespace enc {
 
@@ -115,6 +130,25 @@ struct BlobDesc {
     uint32_t blk0, nblk;
 };
 
+struct Span {            // a DEFLATE span: up to dfl::kSpanSegs segments of one blob
+    uint64_t src;
+    uint32_t len, blob;
+    uint32_t seg0, nseg;
+    uint32_t k;          // span index in its blob
+    uint32_t last;       // the blob's last span: its block carries BFINAL
+};
+
+struct SpanOut {         // what the DEFLATE stages hand on, per span
+    uint32_t fixed_bits, dyn_bits;  // the whole block coded either way (k_dfl_size)
+    uint32_t hdr_bits;              // the dynamic header
+    uint32_t crc;                   // CRC-32 register over the span's bytes from 0, no final inversion
+    uint32_t type, nbits;           // the choice and the block's bits (k_enc_plan)
+    uint64_t bit;                   // where the block starts, in bits from the member's start
+    uint32_t edge_lo, edge_hi;      // its bits in the bytes it shares with its neighbours (k_dfl_emit)
+};
+
+constexpr uint32_t kSpanLens = dfl::kLitSlots + dfl::kDistSlots;  // code lengths kept per span
+
 struct Batch {
     const uint8_t *base;
     uint32_t nblobs, nsegs, nblks, npieces_max;
@@ -141,6 +175,13 @@ struct Batch {
     BlobKey *keys;            // per blob
     uint64_t *status;         // [0]: CDC_E_NOSPACE when out_cap is too small
     const uint32_t *xx_ids;   // XXH32 order of the blobs
+    // GZIP (compress == 2)
+    uint32_t nspans;
+    const Span *spans;
+    const uint32_t *blob_span0;  // nblobs + 1
+    SpanOut *sp;
+    uint8_t *sp_lens;         // kSpanLens per span: literal/length then distance code lengths
+    uint32_t *sp_hdr;         // dfl::kHdrWords per span: the dynamic header's bits
 };
 
 // ---------------------------------------------------------------------------
@@ -580,6 +621,20 @@ __global__ __launch_bounds__(kPlanThreads) void k_enc_plan(const Batch B)
             uint64_t F;
             if (B.compress && D.len == 0) {
                 F = 0;  // DeflateStream of empty input is an empty stream (compression/compression.go:58-62)
+            } else if (B.compress == 2u) {
+                // the member's blocks in order: each span's form is chosen at
+                // the bit where the block before it ends (a stored block's
+                // padding depends on it)
+                uint64_t P = 80;  // after the ten header bytes
+                for (uint32_t sp = B.blob_span0[b]; sp < B.blob_span0[b + 1]; ++sp) {
+                    SpanOut &o = B.sp[sp];
+                    uint64_t bits;
+                    o.type = dfl::choose_block(P, B.spans[sp].len, o.fixed_bits, o.dyn_bits, bits);
+                    o.bit = P;
+                    o.nbits = uint32_t(bits);
+                    P += bits;
+                }
+                F = (P + 7) / 8 + 8;  // CRC-32, ISIZE
             } else if (B.compress) {
                 uint64_t off = 7;
                 for (uint32_t k = 0; k < D.nblk; ++k) {
@@ -1058,6 +1113,233 @@ __global__ __launch_bounds__(kGcmWaves * 64) void k_gcm(const Batch B)
 }
 
 // ---------------------------------------------------------------------------
+// GZIP: DEFLATE over k_lz4_seq's records (deflate_enc.h has every rule), one
+// workgroup per span, lane t the span's stretch t.  These kernels stand after
+// the GCM kernels on purpose: in front of them they moved k_gcm's code in the
+// code object and its time on C3 went from 224 to 259 us, the same
+// instructions.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDflThreads = dfl::kStretches;
+static_assert(kDflThreads == 256 && dfl::kSeg == kSegLZ && kBlockLZ % dfl::kSpan == 0, "a span is four segments of one block");
+
+struct WgPar {
+    uint32_t lane;
+    static constexpr uint32_t nl = kDflThreads;
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ void add(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+    __device__ __forceinline__ void bor(uint32_t *p, uint32_t v) { atomicOr(p, v); }
+};
+
+struct LdsRd {  // the span's bytes in LDS
+    const uint32_t *w;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return (w[i >> 2] >> ((i & 3u) * 8u)) & 255u; }
+};
+
+// The span into LDS, 16 bytes per lane and load (unaligned global loads); the
+// last partial 16 bytes from byte loads, zero-filled.  Nothing past src + n is read.
+__device__ void load_span(uint32_t *data, const uint8_t *src, uint32_t n)
+{
+    for (uint32_t i = threadIdx.x; i < (n + 15) / 16; i += kDflThreads) {
+        const uint32_t p = 16 * i;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (p + 16 <= n) {
+            __builtin_memcpy(&v, src + p, 16);
+        } else {
+            uint32_t w[4] = {0, 0, 0, 0};
+            for (uint32_t b = 0; p + b < n; ++b) w[b >> 2] |= uint32_t(src[p + b]) << (8 * (b & 3));
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        *reinterpret_cast<uint4 *>(&data[4 * i]) = v;
+    }
+}
+
+__device__ __forceinline__ dfl::SpanView span_view(const Batch &B, const Span &S)
+{
+    dfl::SpanView V;
+    for (uint32_t g = 0; g < dfl::kSpanSegs; ++g) {
+        const bool in = g < S.nseg;
+        V.rec[g] = reinterpret_cast<const dfl::Rec *>(B.recs + uint64_t(S.seg0 + (in ? g : 0u)) * kRecCap);
+        V.nrec[g] = in ? B.nrec[S.seg0 + g] : 0u;
+    }
+    V.len = S.len;
+    return V;
+}
+
+// x^(8 bytes) mod P for crc_mul (the polynomial is primitive: exponents count mod 2^32 - 1).
+__device__ __forceinline__ uint32_t crc_shift(uint64_t bytes) { return infw::crc_xpow(uint32_t(8 * bytes % 0xFFFFFFFFull)); }
+
+struct alignas(16) DflSizeLds {
+    uint32_t data[dfl::kSpan / 4];
+    uint32_t lfreq[dfl::kLitSlots], dfreq[dfl::kDistSlots];
+    uint32_t xbits;
+    uint32_t crc[kDflThreads / 64];
+    uint32_t hdr[dfl::kHdrWords];
+    uint8_t llen[dfl::kLitSlots], dlen[dfl::kDistSlots];
+    dfl::CodeWork W;
+    dfl::HdrWork H;
+};
+
+__global__ __launch_bounds__(kDflThreads) void k_dfl_size(const Batch B)
+{
+    __shared__ DflSizeLds L;
+    const uint32_t t = threadIdx.x, sid = blockIdx.x;
+    const Span S = B.spans[sid];
+    WgPar par{t};
+    for (uint32_t i = t; i < dfl::kLitSlots; i += kDflThreads) {
+        L.lfreq[i] = 0;
+        L.llen[i] = 0;
+    }
+    if (t < dfl::kDistSlots) {
+        L.dfreq[t] = 0;
+        L.dlen[t] = 0;
+    }
+    if (t < dfl::kHdrWords) L.hdr[t] = 0;
+    if (t == 0) L.xbits = 0;
+    load_span(L.data, B.base + S.src, S.len);
+    __syncthreads();
+    const dfl::SpanView V = span_view(B, S);
+    LdsRd rd{L.data};
+    dfl::span_hist(par, V, rd, L.lfreq, L.dfreq, &L.xbits);
+    // CRC-32: each lane its stretch from a zero register, moved to the span's
+    // end by x^(8 * bytes after it); the span's register is their sum
+    {
+        const uint32_t a = min(t * dfl::kStretch, S.len), e = min(a + dfl::kStretch, S.len);
+        uint32_t r = 0;
+        for (uint32_t i = a; i < e; ++i) r = infw::crc_bits(r, rd(i));
+        if (r) r = infw::crc_mul(r, crc_shift(S.len - e));
+        for (int o = 32; o; o >>= 1) r ^= __shfl_xor(r, o);
+        if ((t & 63u) == 0) L.crc[t >> 6] = r;
+    }
+    dfl::build_lengths(par, L.lfreq, dfl::kNLit, 15, L.llen, L.W);
+    dfl::build_lengths(par, L.dfreq, dfl::kNDist, 15, L.dlen, L.W);
+    if (t == 0) dfl::header_tokens(L.llen, L.dlen, L.H);
+    dfl::build_lengths(par, L.H.clfreq, dfl::kNCl, 7, L.H.cllen, L.W);
+    dfl::assign_codes(par, L.H.cllen, dfl::kNCl, L.H.clcode);
+    if (t == 0) {
+        SpanOut o{};
+        o.hdr_bits = dfl::write_header(L.H, L.hdr);
+        o.dyn_bits = 3 + o.hdr_bits + dfl::body_bits(L.lfreq, L.dfreq, L.llen, L.dlen, L.xbits);
+        o.fixed_bits = 3 + dfl::body_bits(L.lfreq, L.dfreq, nullptr, nullptr, L.xbits);
+        uint32_t c = 0;
+        for (uint32_t i = 0; i < kDflThreads / 64; ++i) c ^= L.crc[i];
+        o.crc = c;
+        B.sp[sid] = o;
+    }
+    __syncthreads();
+    uint8_t *lens = B.sp_lens + uint64_t(sid) * kSpanLens;
+    for (uint32_t i = t; i < dfl::kLitSlots; i += kDflThreads) lens[i] = L.llen[i];
+    if (t < dfl::kDistSlots) lens[dfl::kLitSlots + t] = L.dlen[t];
+    if (t < dfl::kHdrWords) B.sp_hdr[uint64_t(sid) * dfl::kHdrWords + t] = L.hdr[t];
+}
+
+struct alignas(16) DflEmitLds {
+    uint32_t data[dfl::kSpan / 4];
+    uint32_t out[dfl::kSpan / 4 + 8];  // the block from bit (start & 7): at most 8 * len + 42 + 7 bits, and a word to look ahead
+    uint32_t sbits[dfl::kStretches];
+    uint32_t hdr[dfl::kHdrWords];
+    uint8_t lens[kSpanLens];
+    dfl::Codes C;
+};
+
+__global__ __launch_bounds__(kDflThreads) void k_dfl_emit(const Batch B)
+{
+    __shared__ DflEmitLds L;
+    if (B.status[0]) return;
+    const uint32_t t = threadIdx.x, sid = blockIdx.x;
+    const Span S = B.spans[sid];
+    const SpanOut O = B.sp[sid];
+    uint8_t *dst = frame_ptr(B, S.blob);
+    const uint32_t sh = uint32_t(O.bit & 7u);
+    const uint64_t g = O.bit >> 3;  // the member's byte that holds the block's first bit
+    if (O.type == dfl::kStored) {
+        // 3 header bits at the running position, zeros to the byte boundary, LEN, NLEN, the bytes
+        const uint64_t A = (O.bit + 3 + 7) >> 3;
+        if (t == 0) {
+            const uint32_t h = S.last ? 1u : 0u;
+            if (sh == 0) dst[g] = uint8_t(h);
+            if (sh > 5) dst[g + 1] = uint8_t(h >> (8 - sh));
+            B.sp[sid].edge_lo = sh ? (h << sh) & 255u : 0u;
+            B.sp[sid].edge_hi = 0;
+            dst[A] = uint8_t(S.len);
+            dst[A + 1] = uint8_t(S.len >> 8);
+            dst[A + 2] = uint8_t(~S.len);
+            dst[A + 3] = uint8_t(~S.len >> 8);
+        }
+        copy_span(dst + A + 4, B.base + S.src, S.len, t, kDflThreads);
+        return;
+    }
+    WgPar par{t};
+    const bool dyn = O.type == dfl::kDynamic;
+    for (uint32_t i = t; i < dfl::kSpan / 4 + 8; i += kDflThreads) L.out[i] = 0;
+    load_span(L.data, B.base + S.src, S.len);
+    if (dyn) {
+        for (uint32_t i = t; i < kSpanLens; i += kDflThreads) L.lens[i] = B.sp_lens[uint64_t(sid) * kSpanLens + i];
+        if (t < dfl::kHdrWords) L.hdr[t] = B.sp_hdr[uint64_t(sid) * dfl::kHdrWords + t];
+    }
+    dfl::load_codes(par, L.C, dyn ? L.lens : nullptr, dyn ? L.lens + dfl::kLitSlots : nullptr);
+    const dfl::SpanView V = span_view(B, S);
+    LdsRd rd{L.data};
+    dfl::span_count(par, V, rd, L.C, L.sbits);
+    const uint64_t end = dfl::span_pack(par, V, rd, L.C, L.sbits, O.type, S.last != 0, L.hdr, O.hdr_bits, L.out, sh);
+    // whole bytes out; the first and the last byte, where a neighbour's bits
+    // share them, go to k_gz_fin as edges
+    const uint32_t eb = uint32_t(end), j0 = sh ? 1u : 0u, j1 = eb >> 3;
+    if (t == 0) {
+        B.sp[sid].edge_lo = sh ? L.out[0] & 255u : 0u;
+        B.sp[sid].edge_hi = (eb & 7u) ? (L.out[j1 >> 2] >> ((j1 & 3u) * 8u)) & 255u : 0u;
+    }
+    if (eb != sh + O.nbits || j1 <= j0) return;  // the plan and the packing disagree (a bug): the CRC-32 will say so
+    {
+        uint8_t *o = dst + g + j0;
+        const uint32_t n = j1 - j0;
+        const uint32_t head = min((4u - uint32_t(reinterpret_cast<uintptr_t>(o) & 3u)) & 3u, n);
+        const uint32_t nd = (n - head) >> 2, tail = n - head - 4 * nd;
+        if (t < head) o[t] = uint8_t((L.out[(j0 + t) >> 2] >> (((j0 + t) & 3u) * 8u)) & 255u);
+        uint32_t *ow = reinterpret_cast<uint32_t *>(o + head);
+        for (uint32_t d = t; d < nd; d += kDflThreads) {
+            const uint32_t so = j0 + head + 4 * d;
+            ow[d] = __builtin_amdgcn_alignbit(L.out[(so >> 2) + 1], L.out[so >> 2], (so & 3u) * 8u);
+        }
+        if (t < tail) {
+            const uint32_t so = j0 + head + 4 * nd + t;
+            o[head + 4 * nd + t] = uint8_t((L.out[so >> 2] >> ((so & 3u) * 8u)) & 255u);
+        }
+    }
+}
+
+// One wave per blob: the ten header bytes of Go's gzip.NewWriter (no flags,
+// MTIME 0, XFL 0, OS 255), the bytes that two spans' blocks share, CRC-32 and ISIZE.
+__global__ __launch_bounds__(64) void k_gz_fin(const Batch B)
+{
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (B.status[0] || B.frame_len[b] == 0) return;  // empty blob: an empty stream
+    uint8_t *f = frame_ptr(B, b);
+    const uint64_t len = B.blobs[b].len;
+    const uint32_t s0 = B.blob_span0[b], n = B.blob_span0[b + 1] - s0;
+    if (lane < 10) f[lane] = lane == 0 ? 0x1F : lane == 1 ? 0x8B : lane == 2 ? 8 : lane == 9 ? 0xFF : 0;
+    uint32_t acc = 0;
+    for (uint32_t k = lane; k < n; k += 64) {
+        const SpanOut &o = B.sp[s0 + k];
+        const uint64_t done = min<uint64_t>(len, uint64_t(k + 1) * dfl::kSpan);
+        acc ^= infw::crc_mul(o.crc, crc_shift(len - done));
+        if (k && (o.bit & 7u)) f[o.bit >> 3] = uint8_t(B.sp[s0 + k - 1].edge_hi | o.edge_lo);
+    }
+    for (int o = 32; o; o >>= 1) acc ^= __shfl_xor(acc, o);
+    if (lane == 0) {
+        // the register started from 0xFFFFFFFF, not 0: that start moved past len bytes
+        const uint32_t crc = ~(acc ^ infw::crc_mul(0xFFFFFFFFu, crc_shift(len)));
+        const SpanOut &o = B.sp[s0 + n - 1];
+        const uint64_t E = o.bit + o.nbits;
+        if (E & 7u) f[E >> 3] = uint8_t(o.edge_hi);
+        uint8_t *e = f + ((E + 7) >> 3);
+        for (int i = 0; i < 4; ++i) {
+            e[i] = uint8_t(crc >> (8 * i));
+            e[4 + i] = uint8_t(uint32_t(len) >> (8 * i));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 static std::once_flag g_tab_once;
@@ -1131,6 +1413,13 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                                  uint64_t out_cap, uint64_t *out_offsets, void *stream)
 {
     if ((n && (!d_base || !offsets || !lens || !out_offsets)) || (key && !random) || !d_out) return CDC_E_INVALID;
+    if (device < 0 || device >= 64) return CDC_E_INVALID;
+    // the selector: 0 none, 2 GZIP, every other value LZ4
+    const int mode = compress == CDC_COMPRESS_GZIP ? 2 : compress ? 1 : 0;
+    const bool gzip = mode == 2;
+    if (gzip)
+        for (uint32_t b = 0; b < n; ++b)
+            if (lens[b] > dfl::kMaxBlob) return CDC_E_UNSUPPORTED;  // ISIZE is 32 bits; Decode refuses such a stream
     if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
     int st = ensure_tables();
     if (st != CDC_OK) return st;
@@ -1139,14 +1428,18 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     // plan on the host: blobs, 4-MiB blocks, 8-KiB segments, frame slots.
     // Counted first, then written straight into the pinned staging at their
     // workspace offsets (no vectors, no copy).
-    size_t nk = 0, ng = 0;
+    size_t nk = 0, ng = 0, nsp = 0;
     uint64_t slot = 0, pieces_max = 0;
+    auto frame_max = [&](uint64_t len, uint64_t nblk) {
+        return gzip ? dfl::member_bound(len) : compress ? 7 + 4ull * nblk + len + 8 : len;
+    };
     for (uint32_t b = 0; b < n; ++b) {
         const uint64_t nblk = compress ? (lens[b] + kBlockLZ - 1) / kBlockLZ : 0;
         nk += nblk;
         if (nblk) ng += (nblk - 1) * ((kBlockLZ + kSegLZ - 1) / kSegLZ) +
                         (lens[b] - (nblk - 1) * kBlockLZ + kSegLZ - 1) / kSegLZ;
-        const uint64_t fmax = compress ? 7 + 4ull * nblk + lens[b] + 8 : lens[b];
+        if (gzip) nsp += (lens[b] + dfl::kSpan - 1) / dfl::kSpan;
+        const uint64_t fmax = frame_max(lens[b], nblk);
         slot += align16(fmax);
         pieces_max += encrypt ? (fmax + kPiece - 1) / kPiece : 0;
     }
@@ -1159,13 +1452,15 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
         return o;
     };
     const size_t o_blobs = take(nb * sizeof(BlobDesc)), o_blks = take(nk * sizeof(Blk)), o_segs = take(ng * sizeof(Seg));
+    const size_t o_spans = take(nsp * sizeof(Span)), o_bsp = take(gzip ? (nb + 1) * 4 : 0);
     const size_t o_rnd = take(encrypt ? nb * 56 : 0), o_key = take(32);
     const size_t o_recs = take(ng * kRecCap * sizeof(uint2)), o_nrec = take(ng * 4), o_trail = take(ng * 4),
                  o_sout = take(ng * 4);
     const size_t o_bsz = take(nk * 4), o_bfo = take(nk * 8), o_xxh = take(nb * 4), o_flen = take(nb * 8);
     const size_t o_oo = take((nb + 1) * 8), o_pb = take((nb + 1) * 4), o_keys = take(encrypt ? nb * sizeof(BlobKey) : 0);
-    const size_t o_status = take(16), o_frames = take(encrypt ? slot : 0), o_xx = take(compress ? nb * 4 : 0);
-    if (device < 0 || device >= 64) return CDC_E_INVALID;
+    const size_t o_status = take(16), o_frames = take(encrypt ? slot : 0), o_xx = take(mode == 1 ? nb * 4 : 0);
+    const size_t o_sp = take(nsp * sizeof(SpanOut)), o_splens = take(nsp * kSpanLens),
+                 o_sphdr = take(nsp * dfl::kHdrWords * 4);
     WsCache &C = g_ws[device][cdc::t_encode_ws & 1];
     std::lock_guard<std::mutex> lk(C.mu);
     if (C.cap < off) {
@@ -1183,7 +1478,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     // The plan's tables at their workspace offsets [0, o_key + 32) in pinned
     // staging, XXH32 order after them: two DMAs.  (The call ends with a
     // stream sync under C.mu, so the staging is free again on return.)
-    const size_t h_prefix = o_key + 32, h_xx = align16(h_prefix), h_need = h_xx + (compress ? nb * 4 : 0);
+    const size_t h_prefix = o_key + 32, h_xx = align16(h_prefix), h_need = h_xx + (mode == 1 ? nb * 4 : 0);
     if (C.hcap < h_need) {
         if (C.hp) (void)hipHostFree(C.hp);
         C.hp = nullptr;
@@ -1196,7 +1491,9 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
         BlobDesc *blobs = reinterpret_cast<BlobDesc *>(C.hp + o_blobs);
         Blk *blks = reinterpret_cast<Blk *>(C.hp + o_blks);
         Seg *segs = reinterpret_cast<Seg *>(C.hp + o_segs);
-        uint32_t kb = 0, kg = 0;
+        Span *spans = reinterpret_cast<Span *>(C.hp + o_spans);
+        uint32_t *bsp = reinterpret_cast<uint32_t *>(C.hp + o_bsp);
+        uint32_t kb = 0, kg = 0, ks = 0;
         uint64_t sl = 0;
         for (uint32_t b = 0; b < n; ++b) {
             BlobDesc D{};
@@ -1204,6 +1501,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
             D.len = lens[b];
             D.blk0 = kb;
             D.nblk = compress ? uint32_t((lens[b] + kBlockLZ - 1) / kBlockLZ) : 0u;
+            if (gzip) bsp[b] = ks;
             for (uint32_t k = 0; k < D.nblk; ++k) {
                 Blk K{};
                 K.src = offsets[b] + k * kBlockLZ;
@@ -1212,6 +1510,17 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                 K.k = k;
                 K.seg0 = kg;
                 K.nseg = (K.len + kSegLZ - 1) / kSegLZ;
+                for (uint32_t g = 0; gzip && g < K.nseg; g += dfl::kSpanSegs) {  // a block is whole spans but its last
+                    Span P{};
+                    P.src = K.src + uint64_t(g) * kSegLZ;
+                    P.len = std::min<uint32_t>(dfl::kSpan, K.len - g * kSegLZ);
+                    P.blob = b;
+                    P.seg0 = kg + g;
+                    P.nseg = std::min<uint32_t>(dfl::kSpanSegs, K.nseg - g);
+                    P.k = ks - bsp[b];
+                    P.last = k + 1 == D.nblk && g + dfl::kSpanSegs >= K.nseg;
+                    spans[ks++] = P;
+                }
                 for (uint32_t g = 0; g < K.nseg; ++g) {
                     Seg S{};
                     S.src = K.src + uint64_t(g) * kSegLZ;
@@ -1221,17 +1530,18 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                 }
                 blks[kb++] = K;
             }
-            const uint64_t fmax = compress ? 7 + 4ull * D.nblk + lens[b] + 8 : lens[b];
+            const uint64_t fmax = frame_max(lens[b], D.nblk);
             D.slot = sl;
             sl += align16(fmax);
             blobs[b] = D;
         }
-        if (kb != nk || kg != ng) return CDC_E_INVALID;  // the counting pass and the plan disagree (a bug)
+        if (gzip) bsp[n] = ks;
+        if (kb != nk || kg != ng || ks != nsp) return CDC_E_INVALID;  // the counting pass and the plan disagree (a bug)
         if (encrypt) {
             std::memcpy(C.hp + o_rnd, random, nb * 56);
             std::memcpy(C.hp + o_key, key, 32);
         }
-        if (compress && nb) {
+        if (mode == 1 && nb) {
             // XXH32 order: longest first (a wave's blobs end together); ties by
             // index, so the order is the stable one.  Keys (~len, index) sort
             // without an indirection per comparison.
@@ -1250,7 +1560,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     Bt.nsegs = uint32_t(ng);
     Bt.nblks = uint32_t(nk);
     Bt.npieces_max = uint32_t(pieces_max);
-    Bt.compress = compress ? 1u : 0u;
+    Bt.compress = uint32_t(mode);
     Bt.encrypt = encrypt ? 1u : 0u;
     Bt.blobs = reinterpret_cast<BlobDesc *>(ws + o_blobs);
     Bt.blks = reinterpret_cast<Blk *>(ws + o_blks);
@@ -1273,12 +1583,21 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     Bt.keys = reinterpret_cast<BlobKey *>(ws + o_keys);
     Bt.status = reinterpret_cast<uint64_t *>(ws + o_status);
     Bt.xx_ids = reinterpret_cast<uint32_t *>(ws + o_xx);
+    Bt.nspans = uint32_t(nsp);
+    Bt.spans = reinterpret_cast<Span *>(ws + o_spans);
+    Bt.blob_span0 = reinterpret_cast<uint32_t *>(ws + o_bsp);
+    Bt.sp = reinterpret_cast<SpanOut *>(ws + o_sp);
+    Bt.sp_lens = ws + o_splens;
+    Bt.sp_hdr = reinterpret_cast<uint32_t *>(ws + o_sphdr);
     const uint32_t xx_wgs = (n + kXxWaves * kXxPerWave - 1) / (kXxWaves * kXxPerWave);
     bool ok = hipMemcpyAsync(ws, C.hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
-    if (compress && nb)
+    if (mode == 1 && nb)
         ok = ok && hipMemcpyAsync(ws + o_xx, C.hp + h_xx, nb * 4, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok && n) {
-        if (compress) {
+        if (gzip) {
+            if (ng) hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+            if (nsp) hipLaunchKernelGGL(k_dfl_size, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
+        } else if (compress) {
             ok = hipEventRecord(C.fork, s) == hipSuccess && hipStreamWaitEvent(C.aux, C.fork, 0) == hipSuccess;
             hipLaunchKernelGGL(k_xxh32, dim3(xx_wgs), dim3(kXxWaves * 64), 0, C.aux, Bt);
             ok = ok && hipEventRecord(C.join, C.aux) == hipSuccess;
@@ -1290,7 +1609,10 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
             hipLaunchKernelGGL(k_blob_keys, dim3((n + kKeyThreads - 1) / kKeyThreads), dim3(kKeyThreads), 0, s, Bt);
             hipLaunchKernelGGL(k_blob_pows, dim3((n + kPowWaves - 1) / kPowWaves), dim3(kPowWaves * 64), 0, s, Bt);
         }
-        if (compress) {
+        if (gzip) {
+            if (nsp) hipLaunchKernelGGL(k_dfl_emit, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
+            hipLaunchKernelGGL(k_gz_fin, dim3(n), dim3(64), 0, s, Bt);
+        } else if (compress) {
             if (nk) hipLaunchKernelGGL(k_lz4_emit, dim3(uint32_t(nk), kEmitSplit), dim3(kBlkThreads), 0, s, Bt);
             ok = ok && hipStreamWaitEvent(s, C.join, 0) == hipSuccess;  // the content checksums
             hipLaunchKernelGGL(k_frame_fin, dim3((n + 63) / 64), dim3(64), 0, s, Bt);
@@ -1318,6 +1640,8 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
 
 extern "C" uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt)
 {
-    const uint64_t f = compress ? 7 + 4 * ((len + kBlockLZ - 1) / kBlockLZ) + len + 8 : len;
+    const uint64_t f = compress == CDC_COMPRESS_GZIP ? dfl::member_bound(len)
+                       : compress                    ? 7 + 4 * ((len + kBlockLZ - 1) / kBlockLZ) + len + 8
+                                                     : len;
     return encrypt ? 60 + f + 28 * ((f + kPiece - 1) / kPiece) : f;
 }

@@ -1,6 +1,7 @@
 """Encode on the device: plakar's (*Repository).Encode (repository/repository.go:
 212-236) for a batch of blobs -- the LZ4 frame of compression.DeflateLZ4Stream
-(compression/compression.go:94-106), then the AES-256-GCM stream of
+(compression/compression.go:94-106) or the gzip member of DeflateGzipStream
+(compression.go:78-92), then the AES-256-GCM stream of
 encryption.EncryptStream (encryption/symmetric.go:72-163) when a key is
 configured.  Every call goes through the C ABI (cdc_encode_device)."""
 import ctypes
@@ -145,15 +146,26 @@ def _urandom(n):
     return _reservoir.take(n)
 
 
+def _sel(compress):
+    """The C selector, as decode._sel: False / True (the LZ4 frame) or "GZIP"."""
+    if isinstance(compress, str):
+        return _lib.compress_code(compress)
+    return int(bool(compress))
+
+
 def encode_bound(n, compress=True, encrypt=True):
-    return int(lib().cdc_encode_bound(int(n), int(bool(compress)), int(bool(encrypt))))
+    """An upper bound of one blob's encoded size.  `compress`: False, True (an
+    LZ4 frame) or "GZIP" (a gzip member)."""
+    return int(lib().cdc_encode_bound(int(n), _sel(compress), int(bool(encrypt))))
 
 
 def encode_device(base, offsets, lens, out, key=None, compress=True, random=None, device=0, stream=None):
     """Encode blobs that live in the device tensor `base` (uint8) at the given
     byte offsets/lengths (sequences or numpy arrays) into the device tensor
-    `out`; returns the n + 1 output offsets (int64 numpy array)."""
+    `out`; returns the n + 1 output offsets (int64 numpy array).  `compress`:
+    False, True (an LZ4 frame) or "GZIP" (a gzip member)."""
     import torch
+    sel = _sel(compress)
     ensure_init()
     n = len(lens)
     u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -174,7 +186,7 @@ def encode_device(base, offsets, lens, out, key=None, compress=True, random=None
         else:
             random = bytes(random)
     st = stream if stream is not None else torch.cuda.current_stream(device)
-    check(lib().cdc_encode_device(int(device), ctypes.c_void_p(base.data_ptr()), offs, lns, n, int(bool(compress)),
+    check(lib().cdc_encode_device(int(device), ctypes.c_void_p(base.data_ptr()), offs, lns, n, sel,
                                   key, random if key is not None else None, ctypes.c_void_p(out.data_ptr()),
                                   out.numel(), oo, ctypes.c_void_p(st.cuda_stream)), "cdc_encode_device")
     return oo_a.astype(np.int64)
@@ -182,7 +194,7 @@ def encode_device(base, offsets, lens, out, key=None, compress=True, random=None
 
 def encode_blobs(blobs, key=None, compress=True, random=None, device=0):
     """Encode host byte buffers (numpy uint8 arrays or bytes): a list of the
-    encoded bytes, blob by blob."""
+    encoded bytes, blob by blob.  `compress` as for encode_device."""
     import torch
     arrs = [np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray)) else np.asarray(b, np.uint8).ravel()
             for b in blobs]
@@ -201,15 +213,14 @@ def encode_blobs(blobs, key=None, compress=True, random=None, device=0):
 
 class DeviceEncoder:
     """(*Repository).Encode with the repository's configuration: compression
-    "LZ4" (compression.DefaultConfiguration) or None, and the encryption key
+    "LZ4" (compression.DefaultConfiguration), "GZIP" or None, and the encryption key
     (None: no encryption).  `encode_many` encodes a whole batch of blobs in
     one device call; calling the object encodes one blob, like Encode."""
 
     def __init__(self, key=None, compression="LZ4", device=0):
-        if compression not in (None, "LZ4"):
-            raise ValueError(f"unsupported compression {compression!r} (the device path implements LZ4)")
+        code = _lib.compress_code(compression)  # ValueError for any other name
         self.key = None if key is None else bytes(key)
-        self.compress = compression == "LZ4"
+        self.compress = "GZIP" if code == _lib.CDC_COMPRESS_GZIP else bool(code)
         self.device = device
 
     def encode_many(self, blobs):

@@ -297,7 +297,7 @@ def backup_batch(files, repo: Repository = None, known=None, max_size=None, enco
 
 class BackupSession:
     """A native backup context (cdc_backup_new): the repository's chunking
-    parameters, Encode configuration (compression "LZ4" or None, the 32-byte
+    parameters, Encode configuration (compression "LZ4", "GZIP" or None, the 32-byte
     key or None), the digests already stored (BlobExists), packfile MaxSize
     and the worker counts, with its device buffers kept across runs.  Each
     run() is one backup of a list of files through the pipeline of
@@ -314,13 +314,12 @@ class BackupSession:
         opts = chunkers.ChunkerOpts(MinSize=int(cfg.MinSize), NormalSize=int(cfg.NormalSize),
                                     MaxSize=int(cfg.MaxSize))
         chunkers.Validate(cfg.Algorithm.lower(), opts)
-        if compression not in (None, "LZ4"):
-            raise ValueError(f"unsupported compression {compression!r}")
+        code = _lib.compress_code(compression)  # ValueError for any name but "LZ4", "GZIP" and None
         _lib.ensure_init()
         o = _lib.cdc_backup_opts()
         o.chunking = _lib.cdc_opts(opts.MinSize, opts.NormalSize, opts.MaxSize, 0)
         o.packfile_max = int(packer_mod.DEFAULT_MAX_SIZE if max_size is None else max_size)
-        o.compress = 1 if compression == "LZ4" else 0
+        o.compress = code
         keybuf = knownbuf = None
         if key is not None:
             key = bytes(key)

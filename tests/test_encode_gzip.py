@@ -1,0 +1,324 @@
+"""GZIP Encode on the device (cdc_encode_device with compress =
+CDC_COMPRESS_GZIP) against zlib and inflate_ref: every inflater reads the
+members, the three block forms occur where they should, the ratio conditions,
+the bound and the space check, Decode and the blob check read them back on the
+device, and the backup pipeline writes a GZIP repository that Restore reads."""
+import functools
+import hashlib
+import struct
+import zlib
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import crypto_ref  # noqa: E402
+import inflate_ref as ir  # noqa: E402
+import packfile_ref  # noqa: E402
+from plakar_amd import _lib, decode, encode, snapshot  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+KEY = bytes(range(96, 128))
+HEADER = bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF])
+SPAN = 32768
+SEG = 8192
+SENTINEL = 0x5A
+SLACK = 4096
+WALK_MAX = 70_000  # contents up to this size go through the Python walker, larger ones through zlib only
+
+
+def _encode(blobs, key=None, cap=None, compress="GZIP"):
+    """One cdc_encode_device call over the blobs laid back to back (after one
+    odd byte), into the middle of a sentinel-filled buffer: the encoded blobs.
+    Nothing outside the returned offsets may be written."""
+    lens = np.array([len(b) for b in blobs], dtype=np.uint64)
+    offs = 1 + np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    base = torch.from_numpy(np.frombuffer(b"\xEE" + b"".join(blobs) + b"\xEE", dtype=np.uint8).copy()).cuda()
+    if cap is None:
+        cap = sum(encode.encode_bound(len(b), compress, key is not None) for b in blobs)
+    buf = torch.full((SLACK + cap + SLACK,), SENTINEL, dtype=torch.uint8, device="cuda")
+    oo = encode.encode_device(base, offs[:-1], lens, buf[SLACK:SLACK + cap], key=key, compress=compress)
+    host = buf.cpu().numpy()
+    assert (host[:SLACK] == SENTINEL).all(), "bytes before d_out were written"
+    assert (host[SLACK + int(oo[-1]):] == SENTINEL).all(), "bytes past the last output offset were written"
+    assert oo[0] == 0 and (np.diff(oo) >= 0).all()
+    return [host[SLACK + oo[i]:SLACK + oo[i + 1]].tobytes() for i in range(len(blobs))], offs[:-1]
+
+
+def _period7(n):
+    return (b"abcdefg" * (n // 7 + 1))[:n]
+
+
+@functools.lru_cache(None)
+def _mix():
+    import test_decode_gzip
+    return test_decode_gzip._big()[2][1]
+
+
+@functools.lru_cache(None)
+def _text_mib():
+    return ir.text(1 << 20, 77)
+
+
+def _alternating(spans, seed):
+    """Whole spans of text and of random bytes in turn, then a short text tail."""
+    parts = [ir.text(SPAN, seed + i) if i % 2 == 0 else ir.rnd(SPAN, seed + i) for i in range(spans)]
+    return b"".join(parts) + ir.text(19, seed + 99)
+
+
+@functools.lru_cache(None)
+def _contents():
+    out = []
+    for n in range(81):                                 # their starts: triangular numbers, every residue mod 16
+        out += [bytes(n), b"\x37" * n, ir.text(n, n), _period7(n)]
+    out += [b"\xC3" * n for n in range(250, 801)]       # every match-length residue mod 258
+    for k in range(1, 5):
+        for d in (-13, 13):
+            n = SEG * k + d
+            out += [bytes(n), b"\x37" * n, ir.text(n, 200 + k), _period7(n)]
+    for n in (SPAN - 1, SPAN, SPAN + 1, 2 * SPAN + 5):
+        out += [bytes(n), b"\x37" * n, ir.text(n, 300 + n % 7), _period7(n)]
+    out += [ir.rnd(n, 400 + n % 5) for n in (65535, 65536, 65537)]   # the stored split
+    out += [_text_mib(), _mix(), bytes((4 << 20) + 5)]
+    return out
+
+
+@functools.lru_cache(None)
+def _encoded(sealed):
+    """The shared batch, encoded once per form: (members, contents, source offsets)."""
+    contents = _contents()
+    enc, offs = _encode(contents, key=KEY if sealed else None)
+    if sealed:
+        assert all(len(e) == 60 for e, c in zip(enc, contents) if not c), "an empty blob is the 60-byte header alone"
+        enc = [crypto_ref.decrypt_stream(KEY, e)[0] for e in enc]
+    return enc, contents, offs
+
+
+def _trailer(m):
+    return struct.unpack("<II", m[-8:])
+
+
+@pytest.mark.parametrize("sealed", [False, True], ids=["plain", "sealed"])
+def test_every_inflater_reads_it(sealed):
+    members, contents, offs = _encoded(sealed)
+    assert {int(o) % 16 for o in offs} == set(range(16)), "sources at every offset mod 16"
+    walked = 0
+    for i, (m, c) in enumerate(zip(members, contents)):
+        if not c:
+            assert m == b"", f"blob {i}: an empty blob is an empty stream"
+            continue
+        assert m[:10] == HEADER, f"blob {i}: header"
+        assert zlib.decompress(m, 31) == c, f"blob {i} ({len(c)} bytes): zlib"
+        assert _trailer(m) == (zlib.crc32(c), len(c)), f"blob {i}: trailer"
+        assert len(m) <= encode.encode_bound(len(c), "GZIP", False), f"blob {i}: bound"
+        if len(c) <= WALK_MAX:
+            assert ir.status_of(m) == (0, c), f"blob {i} ({len(c)} bytes): the walker"   # one member, nothing after it
+            walked += len(c)
+    assert walked < 2 << 20
+
+
+def test_sealed_empty_blob_is_the_header_alone():
+    enc, _ = _encode([b"", b"x"], key=KEY)
+    assert len(enc[0]) == 60 and crypto_ref.decrypt_stream(KEY, enc[0])[0] == b""
+
+
+def _blocks(m):
+    """The member's blocks.  The walker stops at the first block with BFINAL, so
+    a walk that yields the whole content and ends right at the trailer also
+    proves BFINAL is set on the last block only; and it refuses a code-length,
+    literal/length or distance set that is not complete (a distance set may be
+    empty or a single one-bit code there: _check_blocks does not allow that)."""
+    out, end, walk = ir.inflate(m, 10)
+    assert end + 8 == len(m), "the last block with BFINAL ends at the trailer"
+    return out, walk
+
+
+def _check_blocks(walk):
+    """What holds for every member: complete code sets, legal matches."""
+    for blk in walk:
+        if blk["btype"] == 2:
+            assert ir.kraft(blk["litlens"]) == 1 << 15, "literal/length set"
+            assert ir.kraft(blk["distlens"]) == 1 << 15, "distance set"
+            assert max(blk["litlens"]) <= 15 and max(blk["distlens"]) <= 15
+        for pos, length, dist in blk["matches"]:
+            assert 3 <= length <= 258 and 1 <= dist <= 32768 and dist <= pos
+
+
+def _first_cl_lengths(m):
+    """The code-length code's lengths of the member's first block (dynamic),
+    read from the bits: BFINAL, BTYPE, HLIT, HDIST, HCLEN, then 3 bits each."""
+    bits = int.from_bytes(m[10:10 + 16], "little")
+    assert (bits >> 1) & 3 == 2
+    ncl = ((bits >> 13) & 15) + 4
+    return [(bits >> (17 + 3 * i)) & 7 for i in range(ncl)]
+
+
+def _member_of(pred):
+    members, contents, _ = _encoded(False)
+    return next((m, c) for m, c in zip(members, contents) if pred(c))
+
+
+def test_structure_occurred():
+    members, contents, _ = _encoded(False)
+    # a random span is stored: 65,536 random bytes are two spans, two stored blocks of a span each
+    m, c = _member_of(lambda c: len(c) == 65536)
+    out, walk = _blocks(m)
+    assert out == c and [(b["btype"], b["stored"]) for b in walk] == [(0, SPAN), (0, SPAN)]
+    m, c = _member_of(lambda c: len(c) == 65537)
+    out, walk = _blocks(m)
+    assert out == c and [(b["btype"], b["stored"]) for b in walk[:2]] == [(0, SPAN), (0, SPAN)] and len(walk) == 3
+    # a tiny blob has one block
+    for m, c in [(m, c) for m, c in zip(members, contents) if 0 < len(c) <= 80][::7]:
+        out, walk = _blocks(m)
+        assert out == c and len(walk) == 1
+        _check_blocks(walk)
+    # text has dynamic blocks with matches in them
+    n = 2 * SPAN + 5
+    m, c = _member_of(lambda c: len(c) == n and c == ir.text(n, 300 + n % 7))
+    out, walk = _blocks(m)
+    assert out == c and [b["btype"] for b in walk[:2]] == [2, 2] and len(walk) == 3
+    _check_blocks(walk)
+    assert all(b["matches"] for b in walk[:2]), "matches were found in text"
+    assert sum(1 << (7 - x) for x in _first_cl_lengths(m) if x) == 1 << 7, "code-length set"
+    # zeros: pairs of 258 bytes and what the split leaves, all at distance 1
+    m, c = _member_of(lambda c: len(c) == SPAN + 1 and not any(c))
+    out, walk = _blocks(m)
+    assert out == c
+    _check_blocks(walk)
+    assert {d for b in walk for _, _, d in b["matches"]} == {1}
+    assert 258 in {ln for b in walk for _, ln, _ in b["matches"]}
+    # a block without matches carries a complete distance set all the same: two one-bit codes
+    c = np.random.default_rng(9).integers(0, 128, 900, dtype=np.uint8).tobytes()   # 7-bit bytes, no 4 bytes twice
+    assert len({c[i:i + 4] for i in range(len(c) - 3)}) == len(c) - 3
+    (m,), _ = _encode([c])
+    out, walk = _blocks(m)
+    assert out == c and [b["btype"] for b in walk] == [2] and not walk[0]["matches"]
+    _check_blocks(walk)
+    assert [x for x in walk[0]["distlens"] if x] == [1, 1]
+
+
+def test_both_kinds_in_one_member_and_mid_byte_stored_blocks():
+    c = _alternating(6, 500)
+    (m,), _ = _encode([c])
+    assert zlib.decompress(m, 31) == c
+    out, end, walk = ir.inflate(m, 10)
+    assert out == c and end + 8 == len(m)
+    kinds = [b["btype"] for b in walk]
+    assert kinds[:6] == [2, 0, 2, 0, 2, 0] and len(kinds) == 7, kinds
+    _check_blocks(walk)
+    # BFINAL only on the last block, and a stored block after a coded one starts
+    # mid-byte: find each stored block's LEN/NLEN and look at the byte before it
+    mid_byte = 0
+    for i in (1, 3, 5):
+        body = c[i * SPAN:(i + 1) * SPAN]
+        at = m.index(body)                      # 32 KiB of random bytes: found once
+        assert m[at - 4:at] == struct.pack("<HH", SPAN, SPAN ^ 0xFFFF)
+        before = m[at - 5]                      # holds the three header bits, then zero padding
+        # some k in 0..7: bits below k belong to the block before, bits k..k+2 are 000, the rest padding
+        ok = [k for k in range(6) if before >> k == 0]
+        assert ok, f"stored block {i}: header and padding are not zero ({before:#x})"
+        mid_byte += before != 0
+    assert mid_byte, "no stored block started inside a byte the block before it had begun"
+    # every block but the last has BFINAL 0: the walker would have stopped early otherwise
+    assert sum(len(b["matches"]) for b in walk) > 100
+
+
+def test_ratio():
+    members, contents, _ = _encoded(False)
+    text, mix, zeros = _text_mib(), _mix(), contents[-1]
+    m_text, m_mix, m_zeros = members[-3], members[-2], members[-1]
+    assert contents[-3] == text and contents[-2] == mix and len(zeros) == (4 << 20) + 5
+
+    def per_segment(c):
+        return sum(len(zlib.compress(c[p:p + SEG], 6)) for p in range(0, len(c), SEG))
+
+    (lz4_text,), _ = _encode([text], compress=True)
+    for name, c, m in (("text", text, m_text), ("mix", mix, m_mix)):
+        seg, full = per_segment(c), len(zlib.compress(c, 6))
+        print(f"{name}: content {len(c)}, device member {len(m)}, zlib-6 per 8-KiB segment {seg}, zlib-6 whole {full}")
+        assert len(c) - len(m) >= (len(c) - seg) / 2, f"{name}: the member saves less than half of what zlib saves per segment"
+    print(f"text: LZ4 frame {len(lz4_text)}; zeros: member {len(m_zeros)}")
+    assert len(m_text) < len(lz4_text), "entropy coding must buy something over the LZ4 frame"
+    assert len(m_zeros) < 64 << 10
+
+
+def test_bound_and_space():
+    blobs = [ir.rnd(n, 600 + i) for i, n in enumerate((1, 2, SEG - 1, SEG, SPAN - 1, SPAN, SPAN + 1, 65535, 65536, 65537,
+                                                         2 * SPAN - 1, 3 * SPAN + 1, 100_003))]
+    blobs += [_alternating(k, 700 + k) for k in (1, 2, 3, 5)]
+    blobs += [(ir.rnd(SPAN, 800) + ir.text(SPAN, 801))[: SPAN + d] for d in (-1, 0, 1, SPAN - 1)]
+    for key in (None, KEY):
+        enc, _ = _encode(blobs, key=key)
+        for e, b in zip(enc, blobs):
+            assert len(e) <= encode.encode_bound(len(b), "GZIP", key is not None), len(b)
+            plain = crypto_ref.decrypt_stream(KEY, e)[0] if key else e
+            assert zlib.decompress(plain, 31) == b
+            assert len(plain) <= len(b) + 18 + 5 * (-(-len(b) // SPAN)), "a span costs at most 5 bytes more than storing nothing"
+    total = sum(len(e) for e in _encode(blobs)[0])
+    with pytest.raises(_lib.CdcError) as e:
+        _encode(blobs, cap=total - 1)
+    assert e.value.status == _lib.CDC_E_NOSPACE
+    assert sum(len(x) for x in _encode(blobs, cap=total)[0]) == total
+
+
+def test_device_to_device():
+    rng = np.random.default_rng(5)
+    blobs = []
+    for i in range(300):
+        n = int(rng.choice([0, 1, 17, 300, 5000, SEG + 3, 40_000, 70_001]))
+        kind = i % 4
+        blobs.append(bytes(n) if kind == 0 else ir.text(n, i) if kind == 1 else ir.rnd(n, i) if kind == 2
+                     else (ir.text(n // 2, i) + ir.rnd(n - n // 2, i)))
+    assert sum(1 for b in blobs if not b) > 5
+    for key in (KEY, None):
+        enc = encode.encode_blobs(blobs, compress="GZIP", key=key)
+        assert decode.decode_blobs(enc, compressed="GZIP", key=key) == blobs
+        sums = [hashlib.sha256(b).digest() for b in blobs]
+        assert (decode.check_blobs(enc, sums, key=key, compressed="GZIP") == 0).all()
+    e = encode.DeviceEncoder(key=KEY, compression="GZIP")
+    d = decode.DeviceDecoder(key=KEY, compression="GZIP")
+    assert d(e(blobs[5])) == blobs[5] and d.decode_many(e.encode_many(blobs[:9])) == blobs[:9]
+
+
+def test_the_selector_selects():
+    c = ir.text(5000, 3)
+    (gz,), _ = _encode([c], compress="GZIP")
+    (lz,), _ = _encode([c], compress=True)
+    (raw,), _ = _encode([c], compress=False)
+    assert gz[:2] == b"\x1f\x8b" and lz[:4] == bytes([0x04, 0x22, 0x4D, 0x18]) and raw == c
+    # every other non-zero value still means LZ4 at the C boundary
+    import ctypes
+    base = torch.from_numpy(np.frombuffer(c, dtype=np.uint8).copy()).cuda()
+    out = torch.zeros(encode.encode_bound(len(c), True, False), dtype=torch.uint8, device="cuda")
+    offs, lens, oo = (ctypes.c_uint64 * 1)(0), (ctypes.c_uint64 * 1)(len(c)), (ctypes.c_uint64 * 2)()
+    rc = _lib.lib().cdc_encode_device(0, ctypes.c_void_p(base.data_ptr()), offs, lens, 1, 7, None, None,
+                                      ctypes.c_void_p(out.data_ptr()), out.numel(), oo,
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0 and out[:oo[1]].cpu().numpy().tobytes() == lz
+
+
+def test_backup_to_restore(tmp_path):
+    files = [ir.text(300_000, 1), ir.rnd(70_000, 2), bytes(200_000), b"", ir.text(300_000, 1), b"tiny",
+             ir.text(90_000, 3) + ir.rnd(90_000, 4), ir.rnd(70_000, 2), ir.text(1234, 5), bytes(200_000),
+             _period7(150_000), ir.text(64_000, 6)]
+    paths = []
+    for i, f in enumerate(files):
+        p = tmp_path / f"f{i}"
+        p.write_bytes(f)
+        paths.append(str(p))
+    for comp in ("GZIP", "LZ4"):
+        objs, packs, _ = snapshot.backup_files(paths, key=KEY, compression=comp, timestamp=3)
+        contents, statuses, _ = snapshot.restore_files(objs, packs, key=KEY, compression=comp)
+        assert statuses == [0] * len(files) and contents == files, comp
+        if comp == "GZIP":
+            pf = packfile_ref.parse(packs[0])
+            assert pf.index
+            for _, csum, off, n in pf.index[:8]:
+                member = crypto_ref.decrypt_stream(KEY, bytes(pf.blobs[off:off + n]))[0]
+                content = zlib.decompress(member, 31) if member else b""
+                assert hashlib.sha256(content).digest() == csum
+    objs, packs = snapshot.backup_batch(files, encode=encode.DeviceEncoder(key=None, compression="GZIP"))
+    contents, statuses, _ = snapshot.restore_files(objs, packs, compression="GZIP")
+    assert statuses == [0] * len(files) and contents == files
