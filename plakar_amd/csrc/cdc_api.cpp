@@ -26,6 +26,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 
 using namespace cdc;
@@ -38,17 +39,15 @@ constexpr uint64_t kDefaultMaskL = 0x0000d90003530000ull;  // FastCDC paper Mask
 // One in-flight launch group of the host-buffer path: device input, workspace,
 // cut lists and results, plus the event that marks its results as copied back.
 struct Slot {
-    uint8_t *d_in = nullptr;
-    uint64_t in_cap = 0;
-    void *d_ws = nullptr;
-    uint64_t ws_cap = 0;
-    cdc_cut *d_cuts = nullptr;
-    cdc_cut *h_cuts = nullptr;
-    uint64_t cuts_cap = 0;
-    cdc_result *d_res = nullptr;
-    cdc_result *h_res = nullptr;
+    DevBuf in, ws, cuts, res;
+    PinBuf cuts_h, res_h;
     hipEvent_t staged = nullptr;  // copy stream: input bytes are on the device
     hipEvent_t done = nullptr;    // compute stream: results are in h_res / h_cuts
+    uint8_t *d_in() const { return in.as<uint8_t>(); }
+    cdc_cut *d_cuts() const { return cuts.as<cdc_cut>(); }
+    cdc_cut *h_cuts() const { return cuts_h.as<cdc_cut>(); }
+    cdc_result *d_res() const { return res.as<cdc_result>(); }
+    cdc_result *h_res() const { return res_h.as<cdc_result>(); }
 };
 
 constexpr int kBounces = 2;
@@ -60,8 +59,7 @@ struct DeviceCtx {
     hipStream_t copy = nullptr;    // host -> device input copies
     std::mutex mu;
     Slot slot[2];
-    uint8_t *bounce[kBounces] = {nullptr, nullptr};  // pinned staging for H2D
-    uint64_t bounce_cap = 0;
+    PinBuf bounce[kBounces];  // pinned staging for H2D, both of one size
     hipEvent_t bounce_ev[kBounces] = {nullptr, nullptr};
     int next_bounce = 0;
     // Adaptive MaskL index (run_group): k_maskl_probe / k_scan_l raise *hint_h
@@ -171,83 +169,43 @@ DevParams make_params(const cdc_opts *o)
         if ((x) != hipSuccess) return CDC_E_DEVICE; \
     } while (0)
 
-void free_slot(Slot &sl)
-{
-    if (sl.d_in) (void)hipFree(sl.d_in);
-    if (sl.d_ws) (void)hipFree(sl.d_ws);
-    if (sl.d_cuts) (void)hipFree(sl.d_cuts);
-    if (sl.h_cuts) (void)hipHostFree(sl.h_cuts);
-    if (sl.d_res) (void)hipFree(sl.d_res);
-    if (sl.h_res) (void)hipHostFree(sl.h_res);
-    if (sl.staged) (void)hipEventDestroy(sl.staged);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-    sl = Slot();
-}
-
+// The context's slots and bounce buffers, back to their first state (the
+// caller has drained the streams).
 void free_ctx_buffers(DeviceCtx *c)
 {
-    for (auto &sl : c->slot) free_slot(sl);
+    for (auto &sl : c->slot) {
+        if (sl.staged) (void)hipEventDestroy(sl.staged);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+        sl = Slot();
+    }
     for (int k = 0; k < kBounces; ++k) {
-        if (c->bounce[k]) (void)hipHostFree(c->bounce[k]);
+        c->bounce[k].release();
         if (c->bounce_ev[k]) (void)hipEventDestroy(c->bounce_ev[k]);
-        c->bounce[k] = nullptr;
         c->bounce_ev[k] = nullptr;
     }
-    c->bounce_cap = 0;
 }
 
-// Grow a slot's buffers; the slot must be idle (its last group harvested).
+// Room in a slot for a launch group; the slot must be idle (its last group harvested).
 int grow_slot(Slot &sl, uint64_t in_bytes, uint64_t ws_bytes, uint64_t ncuts)
 {
     if (!sl.staged) HIPCHK(hipEventCreateWithFlags(&sl.staged, hipEventDisableTiming));
     if (!sl.done) HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (in_bytes > sl.in_cap) {
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        sl.d_in = nullptr;
-        sl.in_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&sl.d_in), in_bytes));
-        sl.in_cap = in_bytes;
-    }
-    if (ws_bytes > sl.ws_cap) {
-        if (sl.d_ws) (void)hipFree(sl.d_ws);
-        sl.d_ws = nullptr;
-        sl.ws_cap = 0;
-        HIPCHK(hipMalloc(&sl.d_ws, ws_bytes));
-        sl.ws_cap = ws_bytes;
-    }
-    if (ncuts > sl.cuts_cap) {
-        if (sl.d_cuts) (void)hipFree(sl.d_cuts);
-        if (sl.h_cuts) (void)hipHostFree(sl.h_cuts);
-        sl.d_cuts = sl.h_cuts = nullptr;
-        sl.cuts_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&sl.d_cuts), ncuts * sizeof(cdc_cut)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&sl.h_cuts), ncuts * sizeof(cdc_cut),
-                             hipHostMallocDefault));
-        sl.cuts_cap = ncuts;
-    }
-    if (!sl.d_res) {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&sl.d_res), kMaxBufsPerLaunch * sizeof(cdc_result)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&sl.h_res),
-                             kMaxBufsPerLaunch * sizeof(cdc_result), hipHostMallocDefault));
-    }
-    return CDC_OK;
+    const bool ok = sl.in.reserve(in_bytes) && sl.ws.reserve(ws_bytes) && sl.cuts.reserve(ncuts * sizeof(cdc_cut)) &&
+                    sl.cuts_h.reserve(ncuts * sizeof(cdc_cut)) && sl.res.reserve(kMaxBufsPerLaunch * sizeof(cdc_result)) &&
+                    sl.res_h.reserve(kMaxBufsPerLaunch * sizeof(cdc_result));
+    return ok ? CDC_OK : CDC_E_DEVICE;
 }
 
+// Both bounce buffers of at least `bytes`, once the copies out of them are done.
 int grow_bounce(DeviceCtx *c, uint64_t bytes)
 {
-    if (bytes <= c->bounce_cap) return CDC_OK;
+    if (c->bounce[kBounces - 1].data() && bytes <= c->bounce[kBounces - 1].cap()) return CDC_OK;
     HIPCHK(hipStreamSynchronize(c->copy));
     for (int k = 0; k < kBounces; ++k) {
-        if (c->bounce[k]) (void)hipHostFree(c->bounce[k]);
-        c->bounce[k] = nullptr;
-    }
-    c->bounce_cap = 0;
-    for (int k = 0; k < kBounces; ++k) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->bounce[k]), bytes, hipHostMallocDefault));
+        if (!c->bounce[k].reserve(bytes)) return CDC_E_DEVICE;
         if (!c->bounce_ev[k]) HIPCHK(hipEventCreateWithFlags(&c->bounce_ev[k], hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->bounce_ev[k], c->copy));
     }
-    c->bounce_cap = bytes;
     return CDC_OK;
 }
 
@@ -432,9 +390,9 @@ int stage(DeviceCtx *c, uint8_t *d_dst, const uint8_t *src, uint64_t len)
         const int k = c->next_bounce;
         c->next_bounce = (k + 1) % kBounces;
         HIPCHK(hipEventSynchronize(c->bounce_ev[k]));
-        const uint64_t n = std::min(c->bounce_cap, len - off);
-        par_memcpy(c->bounce[k], src + off, n);
-        HIPCHK(hipMemcpyAsync(d_dst + off, c->bounce[k], n, hipMemcpyHostToDevice, c->copy));
+        const uint64_t n = std::min<uint64_t>(c->bounce[k].cap(), len - off);
+        par_memcpy(c->bounce[k].as<uint8_t>(), src + off, n);
+        HIPCHK(hipMemcpyAsync(d_dst + off, c->bounce[k].data(), n, hipMemcpyHostToDevice, c->copy));
         HIPCHK(hipEventRecord(c->bounce_ev[k], c->copy));
         off += n;
     }
@@ -463,27 +421,27 @@ int run_windowed(DeviceCtx *ctx, const DevParams &P, const cdc_opts *o, HostJob 
         if (st != CDC_OK) return st;
         st = grow_slot(sl, window, need, ncap);
         if (st != CDC_OK) return st;
-        st = stage(ctx, sl.d_in, job->data + off, w);
+        st = stage(ctx, sl.d_in(), job->data + off, w);
         if (st != CDC_OK) return st;
         HIPCHK(hipEventRecord(sl.staged, ctx->copy));
         HIPCHK(hipStreamWaitEvent(ctx->stream, sl.staged, 0));
-        const void *dp = sl.d_in;
-        cdc_cut *cp = sl.d_cuts;
-        const uint64_t cap = sl.cuts_cap;
-        cdc_result *rp = sl.d_res;
-        st = run_group(ctx, P, &dp, &w, 1, fin, &cp, &cap, &rp, sl.d_ws, sl.ws_cap, ctx->stream);
+        const void *dp = sl.d_in();
+        cdc_cut *cp = sl.d_cuts();
+        const uint64_t cap = sl.cuts.cap() / sizeof(cdc_cut);
+        cdc_result *rp = sl.d_res();
+        st = run_group(ctx, P, &dp, &w, 1, fin, &cp, &cap, &rp, sl.ws.data(), sl.ws.cap(), ctx->stream);
         if (st != CDC_OK) return st;
-        HIPCHK(hipMemcpyAsync(sl.h_res, sl.d_res, sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_res(), sl.d_res(), sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        const cdc_result r = sl.h_res[0];
+        const cdc_result r = sl.h_res()[0];
         if (r.status != CDC_OK) return int(r.status);
         if (r.ncuts) {
-            HIPCHK(hipMemcpyAsync(sl.h_cuts, sl.d_cuts, r.ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost,
+            HIPCHK(hipMemcpyAsync(sl.h_cuts(), sl.d_cuts(), r.ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost,
                                   ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
         }
         for (uint64_t k = 0; k < r.ncuts; ++k) {
-            cdc_cut c = sl.h_cuts[k];
+            cdc_cut c = sl.h_cuts()[k];
             c.offset += off;
             job->cuts.push_back(c);
         }
@@ -519,9 +477,9 @@ int run_host_jobs(DeviceCtx *ctx, const cdc_opts *o, std::vector<HostJob *> &job
         Slot &sl = ctx->slot[s];
         HIPCHK(hipEventSynchronize(sl.done));
         for (size_t i = 0; i < pd.jobs.size(); ++i) {
-            const cdc_result r = sl.h_res[i];
+            const cdc_result r = sl.h_res()[i];
             if (r.status != CDC_OK) return int(r.status);
-            pd.jobs[i]->cuts.assign(sl.h_cuts + pd.cut_off[i], sl.h_cuts + pd.cut_off[i] + r.ncuts);
+            pd.jobs[i]->cuts.assign(sl.h_cuts() + pd.cut_off[i], sl.h_cuts() + pd.cut_off[i] + r.ncuts);
         }
         return CDC_OK;
     };
@@ -559,22 +517,22 @@ int run_host_jobs(DeviceCtx *ctx, const cdc_opts *o, std::vector<HostJob *> &job
         if ((st = group_ws_bytes(lens.data(), n, P, &need)) != CDC_OK) return st;
         if ((st = grow_slot(sl, used, need, ncuts)) != CDC_OK) return st;
         for (int i = 0; i < n; ++i)
-            if ((st = stage(ctx, sl.d_in + offs[i], group[i]->data, lens[i])) != CDC_OK) return st;
+            if ((st = stage(ctx, sl.d_in() + offs[i], group[i]->data, lens[i])) != CDC_OK) return st;
         HIPCHK(hipEventRecord(sl.staged, ctx->copy));
         HIPCHK(hipStreamWaitEvent(ctx->stream, sl.staged, 0));
         std::vector<const void *> dp(n);
         std::vector<cdc_cut *> cp(n);
         std::vector<cdc_result *> rp(n);
         for (int i = 0; i < n; ++i) {
-            dp[i] = sl.d_in + offs[i];
-            cp[i] = sl.d_cuts + cut_off[i];
-            rp[i] = sl.d_res + i;
+            dp[i] = sl.d_in() + offs[i];
+            cp[i] = sl.d_cuts() + cut_off[i];
+            rp[i] = sl.d_res() + i;
         }
-        st = run_group(ctx, P, dp.data(), lens.data(), n, 1, cp.data(), caps.data(), rp.data(), sl.d_ws,
-                       sl.ws_cap, ctx->stream);
+        st = run_group(ctx, P, dp.data(), lens.data(), n, 1, cp.data(), caps.data(), rp.data(), sl.ws.data(),
+                       sl.ws.cap(), ctx->stream);
         if (st != CDC_OK) return st;
-        HIPCHK(hipMemcpyAsync(sl.h_res, sl.d_res, n * sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(sl.h_cuts, sl.d_cuts, ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(sl.h_res(), sl.d_res(), n * sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_cuts(), sl.d_cuts(), ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost,
                               ctx->stream));
         HIPCHK(hipEventRecord(sl.done, ctx->stream));
         pend[s].active = true;
@@ -625,9 +583,9 @@ int pipeline_device(int di, const cdc_opts *o, BatchSource &src)
         int st = hipEventSynchronize(sl.done) == hipSuccess ? CDC_OK : CDC_E_DEVICE;
         for (size_t i = 0; i < fl[s].size(); ++i) {
             HostBuf *h = fl[s][i];
-            const cdc_result r = sl.h_res[i];
+            const cdc_result r = sl.h_res()[i];
             h->status = st != CDC_OK ? st : int(r.status);
-            if (h->status == CDC_OK) h->cuts.assign(sl.h_cuts + cut_off[s][i], sl.h_cuts + cut_off[s][i] + r.ncuts);
+            if (h->status == CDC_OK) h->cuts.assign(sl.h_cuts() + cut_off[s][i], sl.h_cuts() + cut_off[s][i] + r.ncuts);
         }
         src.finished(fl[s]);
         fl[s].clear();
@@ -662,22 +620,22 @@ int pipeline_device(int di, const cdc_opts *o, BatchSource &src)
         if (st != CDC_OK) return st;
         if ((st = grow_slot(sl, std::max<uint64_t>(used, 256), need, ncuts)) != CDC_OK) return st;
         for (int i = 0; i < n; ++i)
-            if (lens[i] && (st = stage(ctx, sl.d_in + offs[i], b[i]->data, lens[i])) != CDC_OK) return st;
+            if (lens[i] && (st = stage(ctx, sl.d_in() + offs[i], b[i]->data, lens[i])) != CDC_OK) return st;
         HIPCHK(hipEventRecord(sl.staged, ctx->copy));
         HIPCHK(hipStreamWaitEvent(ctx->stream, sl.staged, 0));
         std::vector<const void *> dp(n);
         std::vector<cdc_cut *> cp(n);
         std::vector<cdc_result *> rp(n);
         for (int i = 0; i < n; ++i) {
-            dp[i] = sl.d_in + offs[i];
-            cp[i] = sl.d_cuts + cut_off[s][i];
-            rp[i] = sl.d_res + i;
+            dp[i] = sl.d_in() + offs[i];
+            cp[i] = sl.d_cuts() + cut_off[s][i];
+            rp[i] = sl.d_res() + i;
         }
-        st = run_group(ctx, P, dp.data(), lens.data(), n, 1, cp.data(), caps.data(), rp.data(), sl.d_ws, sl.ws_cap,
+        st = run_group(ctx, P, dp.data(), lens.data(), n, 1, cp.data(), caps.data(), rp.data(), sl.ws.data(), sl.ws.cap(),
                        ctx->stream);
         if (st != CDC_OK) return st;
-        HIPCHK(hipMemcpyAsync(sl.h_res, sl.d_res, n * sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(sl.h_cuts, sl.d_cuts, ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_res(), sl.d_res(), n * sizeof(cdc_result), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sl.h_cuts(), sl.d_cuts(), ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipEventRecord(sl.done, ctx->stream));
         fl[s] = std::move(b);
         active[s] = true;
@@ -1099,17 +1057,20 @@ struct HybridScratch {
     hipStream_t side = nullptr;
     hipEvent_t ev_dig = nullptr;
     hipEvent_t ev_part[4] = {};
-    // device / pinned host buffers and their capacities in bytes
-    void *d_cuts = nullptr, *d_stage = nullptr, *d_gj = nullptr, *d_sj = nullptr, *d_dig = nullptr;
-    void *h_stage = nullptr, *h_gj = nullptr, *h_sj = nullptr, *h_dig = nullptr;
-    uint64_t c_cuts = 0, c_stage = 0, c_gj = 0, c_sj = 0, c_dig = 0;
-    uint64_t hc_stage = 0, hc_gj = 0, hc_sj = 0, hc_dig = 0;
+    DevBuf d_cuts, d_stage, d_gj, d_sj, d_dig;
+    PinBuf h_stage, h_gj, h_sj, h_dig;
+    // room for `need` bytes, with a quarter's slack when it has to grow
+    template <class B>
+    static bool grow(B &b, uint64_t need)
+    {
+        return b.reserve(need, need + need / 4 + 256);
+    }
 };
 
 HybridScratch &hybrid_scratch(int device)
 {
-    static HybridScratch h[64];
-    return h[device & 63];
+    static HybridScratch *h = new HybridScratch[kMaxDevices];  // never destroyed (DevBuf)
+    return h[unsigned(device) % kMaxDevices];
 }
 
 // Host threads for the hybrid digests' SHA-256, kept between calls (one pool
@@ -1174,32 +1135,8 @@ struct HostPool {
 
 HostPool &host_pool(int device)
 {
-    static HostPool *p = new HostPool[64];  // never destroyed: its threads outlive static destruction
-    return p[device & 63];
-}
-
-bool hy_dev(void *&p, uint64_t &cap, uint64_t need)
-{
-    if (need <= cap && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const uint64_t n = need + need / 4 + 256;
-    if (hipMalloc(&p, n) != hipSuccess) return false;
-    cap = n;
-    return true;
-}
-
-bool hy_host(void *&p, uint64_t &cap, uint64_t need)
-{
-    if (need <= cap && p) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const uint64_t n = need + need / 4 + 256;
-    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return false;
-    cap = n;
-    return true;
+    static HostPool *p = new HostPool[kMaxDevices];  // never destroyed: its threads outlive static destruction
+    return p[unsigned(device) % kMaxDevices];
 }
 
 // One host core's SHA-256 rate, measured once per process (8 MiB through the
@@ -1343,17 +1280,16 @@ int cdc_chunk_digests_hybrid(int device, const void *const *d_data, const uint64
         soff[j] = hbytes;
         hbytes += (L[order[j]] + 15) & ~15ull;
     }
-    if (!hy_dev(H.d_cuts, H.c_cuts, total * sizeof(cdc_cut)) || !hy_dev(H.d_stage, H.c_stage, hbytes + 64) ||
-        !hy_host(H.h_stage, H.hc_stage, hbytes + 64) || !hy_dev(H.d_gj, H.c_gj, k * sizeof(GatherJob)) ||
-        !hy_host(H.h_gj, H.hc_gj, k * sizeof(GatherJob)) || !hy_dev(H.d_sj, H.c_sj, k * sizeof(ScatterJob)) ||
-        !hy_host(H.h_sj, H.hc_sj, k * sizeof(ScatterJob)) || !hy_dev(H.d_dig, H.c_dig, 32 * k) ||
-        !hy_host(H.h_dig, H.hc_dig, 32 * k))
+    if (!H.grow(H.d_cuts, total * sizeof(cdc_cut)) || !H.grow(H.d_stage, hbytes + 64) ||
+        !H.grow(H.h_stage, hbytes + 64) || !H.grow(H.d_gj, k * sizeof(GatherJob)) ||
+        !H.grow(H.h_gj, k * sizeof(GatherJob)) || !H.grow(H.d_sj, k * sizeof(ScatterJob)) ||
+        !H.grow(H.h_sj, k * sizeof(ScatterJob)) || !H.grow(H.d_dig, 32 * k) || !H.grow(H.h_dig, 32 * k))
         return CDC_E_DEVICE;
-    cdc_cut *dcuts = static_cast<cdc_cut *>(H.d_cuts);
-    uint8_t *dstage = static_cast<uint8_t *>(H.d_stage), *hstage = static_cast<uint8_t *>(H.h_stage);
-    GatherJob *hgj = static_cast<GatherJob *>(H.h_gj), *dgj = static_cast<GatherJob *>(H.d_gj);
-    ScatterJob *hsj = static_cast<ScatterJob *>(H.h_sj), *dsj = static_cast<ScatterJob *>(H.d_sj);
-    uint8_t *hdig = static_cast<uint8_t *>(H.h_dig), *ddig = static_cast<uint8_t *>(H.d_dig);
+    cdc_cut *dcuts = H.d_cuts.as<cdc_cut>();
+    uint8_t *dstage = H.d_stage.as<uint8_t>(), *hstage = H.h_stage.as<uint8_t>();
+    GatherJob *hgj = H.h_gj.as<GatherJob>(), *dgj = H.d_gj.as<GatherJob>();
+    ScatterJob *hsj = H.h_sj.as<ScatterJob>(), *dsj = H.d_sj.as<ScatterJob>();
+    uint8_t *hdig = H.h_dig.as<uint8_t>(), *ddig = H.d_dig.as<uint8_t>();
     // From the first enqueue on, every return drains both streams: copies out
     // of the scratch buffers (and gathers from the caller's data) must not
     // outlive this call, whose scratch the next call may free or reuse.
@@ -1779,13 +1715,11 @@ struct cdc_stream {
     cdc_opts opts{};
     DevParams P{};
     uint64_t win = 0;
-    uint8_t *h_win = nullptr;  // pinned window; chunks alias it
-    uint8_t *d_win = nullptr;
-    void *d_ws = nullptr;
-    uint64_t ws_bytes = 0;
-    cdc_cut *d_cuts = nullptr, *h_cuts = nullptr;
+    PinBuf win_h;  // pinned window; chunks alias it
+    DevBuf win_d, ws, cuts_d, res_d;
+    PinBuf cuts_h, res_h;
     uint64_t cuts_cap = 0;
-    cdc_result *d_res = nullptr, *h_res = nullptr;
+    uint8_t *h_win() const { return win_h.as<uint8_t>(); }
     hipStream_t stream = nullptr;
     uint64_t fill = 0;      // bytes in the window
     uint64_t consumed = 0;  // bytes covered by decided chunks of the last run
@@ -1799,15 +1733,8 @@ static void stream_release(cdc_stream *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->h_win) (void)hipHostFree(s->h_win);
-    if (s->d_win) (void)hipFree(s->d_win);
-    if (s->d_ws) (void)hipFree(s->d_ws);
-    if (s->d_cuts) (void)hipFree(s->d_cuts);
-    if (s->h_cuts) (void)hipHostFree(s->h_cuts);
-    if (s->d_res) (void)hipFree(s->d_res);
-    if (s->h_res) (void)hipHostFree(s->h_res);
     if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;  // its buffers go with it
 }
 
 extern "C" int cdc_stream_new(const char *algorithm, const cdc_opts *opts, uint64_t window_bytes,
@@ -1828,18 +1755,13 @@ extern "C" int cdc_stream_new(const char *algorithm, const cdc_opts *opts, uint6
     w = std::max<uint64_t>(w, 2ull * opts->max_size + 4096);
     s->win = w;
     s->cuts_cap = w / opts->min_size + 2;
+    uint64_t ws_bytes = 0;
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&s->h_win), w, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s->d_win), w) != hipSuccess ||
-        cdc_device_workspace_size(w, opts, &s->ws_bytes) != CDC_OK ||
-        hipMalloc(&s->d_ws, s->ws_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s->d_cuts), s->cuts_cap * sizeof(cdc_cut)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&s->h_cuts), s->cuts_cap * sizeof(cdc_cut),
-                      hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&s->d_res), sizeof(cdc_result)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&s->h_res), sizeof(cdc_result),
-                      hipHostMallocDefault) != hipSuccess) {
+        !s->win_h.reserve(w) || !s->win_d.reserve(w) || cdc_device_workspace_size(w, opts, &ws_bytes) != CDC_OK ||
+        !s->ws.reserve(ws_bytes) || !s->cuts_d.reserve(s->cuts_cap * sizeof(cdc_cut)) ||
+        !s->cuts_h.reserve(s->cuts_cap * sizeof(cdc_cut)) || !s->res_d.reserve(sizeof(cdc_result)) ||
+        !s->res_h.reserve(sizeof(cdc_result))) {
         stream_release(s);
         return CDC_E_DEVICE;
     }
@@ -1852,13 +1774,13 @@ extern "C" int cdc_stream_buffer(cdc_stream *s, uint8_t **write_ptr, uint64_t *s
     if (!s || !write_ptr || !space) return CDC_E_INVALID;
     // drop the bytes of chunks already handed out once every decided chunk was served
     if (s->ran && s->next_cut >= s->ncuts && s->consumed) {
-        std::memmove(s->h_win, s->h_win + s->consumed, s->fill - s->consumed);
+        std::memmove(s->h_win(), s->h_win() + s->consumed, s->fill - s->consumed);
         s->fill -= s->consumed;
         s->consumed = 0;
         s->ncuts = s->next_cut = 0;
         s->ran = false;
     }
-    *write_ptr = s->h_win + s->fill;
+    *write_ptr = s->h_win() + s->fill;
     *space = s->win - s->fill;
     return CDC_OK;
 }
@@ -1880,25 +1802,23 @@ static int stream_run(cdc_stream *s)
     uint64_t need = 0;
     int wst = cdc_device_workspace_size(s->fill, &s->opts, &need);
     if (wst != CDC_OK) return wst;
-    if (need > s->ws_bytes) {
+    if (need > s->ws.cap()) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->d_ws) (void)hipFree(s->d_ws);
-        s->d_ws = nullptr;
-        s->ws_bytes = 0;
-        if (hipMalloc(&s->d_ws, need) != hipSuccess) return CDC_E_NOMEM;
-        s->ws_bytes = need;
+        if (!s->ws.reserve(need)) return CDC_E_NOMEM;
     }
-    HIPCHK(hipMemcpyAsync(s->d_win, s->h_win, s->fill, hipMemcpyHostToDevice, s->stream));
-    const int st = cdc_chunk_device_async(s->device, s->d_win, s->fill, s->eof ? 1 : 0, &s->opts,
-                                          s->d_cuts, s->cuts_cap, s->d_res, s->d_ws, s->ws_bytes,
+    cdc_cut *const d_cuts = s->cuts_d.as<cdc_cut>();
+    cdc_result *const d_res = s->res_d.as<cdc_result>();
+    HIPCHK(hipMemcpyAsync(s->win_d.data(), s->h_win(), s->fill, hipMemcpyHostToDevice, s->stream));
+    const int st = cdc_chunk_device_async(s->device, s->win_d.data(), s->fill, s->eof ? 1 : 0, &s->opts,
+                                          d_cuts, s->cuts_cap, d_res, s->ws.data(), s->ws.cap(),
                                           s->stream);
     if (st != CDC_OK) return st;
-    HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, sizeof(cdc_result), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->res_h.data(), d_res, sizeof(cdc_result), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    const cdc_result r = *s->h_res;
+    const cdc_result r = *s->res_h.as<cdc_result>();
     if (r.status != CDC_OK) return int(r.status);
     if (r.ncuts)
-        HIPCHK(hipMemcpy(s->h_cuts, s->d_cuts, r.ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(s->cuts_h.data(), d_cuts, r.ncuts * sizeof(cdc_cut), hipMemcpyDeviceToHost));
     s->ncuts = r.ncuts;
     s->next_cut = 0;
     s->consumed = s->eof ? s->fill : r.consumed;
@@ -1913,14 +1833,14 @@ extern "C" int cdc_stream_next(cdc_stream *s, const uint8_t **chunk, uint64_t *l
     *len = 0;
     for (;;) {
         if (s->ran && s->next_cut < s->ncuts) {
-            const cdc_cut c = s->h_cuts[s->next_cut++];
-            *chunk = s->h_win + c.offset;
+            const cdc_cut c = s->cuts_h.as<cdc_cut>()[s->next_cut++];
+            *chunk = s->h_win() + c.offset;
             *len = c.length;
             return CDC_OK;
         }
         if (s->ran) {
             // every decided chunk served: drop them from the window
-            std::memmove(s->h_win, s->h_win + s->consumed, s->fill - s->consumed);
+            std::memmove(s->h_win(), s->h_win() + s->consumed, s->fill - s->consumed);
             s->fill -= s->consumed;
             s->consumed = 0;
             s->ncuts = s->next_cut = 0;

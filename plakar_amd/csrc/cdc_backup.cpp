@@ -52,6 +52,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 
 namespace {
@@ -140,20 +141,32 @@ struct Batch {
 
 // Buffers of one pipeline slot.  Kept by the context across runs and grown
 // on demand (pinned allocations are slow: they are made once per session).
+// A buffer that reads as the typed pointer its users index and pass on.
+template <class B, class T>
+struct Typed : B {
+    operator T *() const { return this->template as<T>(); }
+};
+template <class T>
+using Dev = Typed<cdc::DevBuf, T>;
+template <class T>
+using Pin = Typed<cdc::PinBuf, T>;
+
 struct Slot {
-    uint8_t *h_arena = nullptr, *d_in = nullptr;
-    uint64_t arena_cap = 0;
-    void *d_ws = nullptr;
-    uint64_t ws_cap = 0;
-    cdc_cut *d_cuts = nullptr, *h_cuts = nullptr, *d_acuts = nullptr;  // file-relative; arena-relative
-    uint64_t *h_meta = nullptr, *d_meta = nullptr;                        // (cut0, cap, arena_off) per file
-    cdc_result *d_res = nullptr, *h_res = nullptr;
-    uint8_t *d_dig = nullptr, *h_dig = nullptr;
-    uint32_t *d_hist = nullptr, *h_hist = nullptr;
-    double *d_ent = nullptr, *h_ent = nullptr;
-    uint64_t cuts_cap = 0, res_cap = 0;
-    uint8_t *d_enc = nullptr, *h_enc = nullptr;
-    uint64_t enc_cap = 0, henc_cap = 0;
+    Pin<uint8_t> h_arena;
+    Dev<uint8_t> d_in;
+    Dev<void> d_ws;
+    Dev<cdc_cut> d_cuts, d_acuts;  // file-relative; arena-relative
+    Pin<cdc_cut> h_cuts;
+    Pin<uint64_t> h_meta;  // (cut0, cap, arena_off) per file
+    Dev<uint64_t> d_meta;
+    Dev<cdc_result> d_res;
+    Pin<cdc_result> h_res;
+    Dev<uint8_t> d_dig, d_enc;
+    Pin<uint8_t> h_dig, h_enc;
+    Dev<uint32_t> d_hist;
+    Pin<uint32_t> h_hist;
+    Dev<double> d_ent;
+    Pin<double> h_ent;
     // A: H2D start / end, cut points end; D: digests start / end, lists back
     hipEvent_t ev[6] = {};
     hipEvent_t ev_enc = nullptr;  // E: the encoded blobs back
@@ -194,87 +207,21 @@ constexpr int kBackupScanTpw = 2;
         if ((x) != hipSuccess) return CDC_E_DEVICE;      \
     } while (0)
 
-template <typename T>
-int grow_dev(T *&p, uint64_t &cap, uint64_t need)
-{
-    if (need <= cap && p) return CDC_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIPOK(hipMalloc(reinterpret_cast<void **>(&p), need ? need : 1));
-    cap = need;
-    return CDC_OK;
-}
-
-template <typename T>
-int grow_host(T *&p, uint64_t need, uint64_t have)
-{
-    if (need <= have && p) return CDC_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    HIPOK(hipHostMalloc(reinterpret_cast<void **>(&p), need ? need : 1, hipHostMallocDefault));
-    return CDC_OK;
-}
-
+// Room in a slot for a batch: every buffer grows on its own, to the exact size.
 int grow_slot(Slot &s, uint64_t arena, uint64_t ws, uint64_t ncuts, uint64_t nfiles)
 {
-    int st;
     if (!s.ev[0]) {
         for (auto &e : s.ev) HIPOK(hipEventCreate(&e));
         HIPOK(hipEventCreateWithFlags(&s.ev_enc, hipEventDisableTiming));
     }
-    if (arena > s.arena_cap || !s.h_arena) {
-        if ((st = grow_host(s.h_arena, arena, 0)) != CDC_OK) return st;
-        uint64_t c = s.arena_cap;
-        if ((st = grow_dev(s.d_in, c, arena)) != CDC_OK) return st;
-        s.arena_cap = arena;
-    }
-    if ((st = grow_dev(s.d_ws, s.ws_cap, std::max<uint64_t>(ws, 256))) != CDC_OK) return st;
-    if (ncuts > s.cuts_cap || !s.h_cuts) {
-        uint64_t c = s.cuts_cap * sizeof(cdc_cut);
-        if ((st = grow_dev(s.d_cuts, c, ncuts * sizeof(cdc_cut))) != CDC_OK) return st;
-        if ((st = grow_host(s.h_cuts, ncuts * sizeof(cdc_cut), 0)) != CDC_OK) return st;
-        c = s.cuts_cap * sizeof(cdc_cut);
-        if ((st = grow_dev(s.d_acuts, c, ncuts * sizeof(cdc_cut))) != CDC_OK) return st;
-        c = s.cuts_cap * 32;
-        if ((st = grow_dev(s.d_dig, c, ncuts * 32)) != CDC_OK) return st;
-        if ((st = grow_host(s.h_dig, ncuts * 32, 0)) != CDC_OK) return st;
-        c = s.cuts_cap * 1024;
-        if ((st = grow_dev(s.d_hist, c, ncuts * 1024)) != CDC_OK) return st;
-        if ((st = grow_host(s.h_hist, ncuts * 1024, 0)) != CDC_OK) return st;
-        c = s.cuts_cap * 8;
-        if ((st = grow_dev(s.d_ent, c, ncuts * 8)) != CDC_OK) return st;
-        if ((st = grow_host(s.h_ent, ncuts * 8, 0)) != CDC_OK) return st;
-        s.cuts_cap = ncuts;
-    }
-    if (nfiles > s.res_cap || !s.h_res) {
-        uint64_t c = s.res_cap * sizeof(cdc_result);
-        if ((st = grow_dev(s.d_res, c, nfiles * sizeof(cdc_result))) != CDC_OK) return st;
-        if ((st = grow_host(s.h_res, nfiles * sizeof(cdc_result), 0)) != CDC_OK) return st;
-        c = s.res_cap * 24;
-        if ((st = grow_dev(s.d_meta, c, nfiles * 24)) != CDC_OK) return st;
-        if ((st = grow_host(s.h_meta, nfiles * 24, 0)) != CDC_OK) return st;
-        s.res_cap = nfiles;
-    }
-    return CDC_OK;
-}
-
-void free_slot(Slot &s)
-{
-    for (void *p : {static_cast<void *>(s.d_in), s.d_ws, static_cast<void *>(s.d_cuts), static_cast<void *>(s.d_res),
-                    static_cast<void *>(s.d_acuts), static_cast<void *>(s.d_meta),
-                    static_cast<void *>(s.d_dig), static_cast<void *>(s.d_hist), static_cast<void *>(s.d_ent),
-                    static_cast<void *>(s.d_enc)})
-        if (p) (void)hipFree(p);
-    for (void *p : {static_cast<void *>(s.h_arena), static_cast<void *>(s.h_cuts), static_cast<void *>(s.h_res),
-                    static_cast<void *>(s.h_meta),
-                    static_cast<void *>(s.h_dig), static_cast<void *>(s.h_hist), static_cast<void *>(s.h_ent),
-                    static_cast<void *>(s.h_enc)})
-        if (p) (void)hipHostFree(p);
-    for (auto &e : s.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s.ev_enc) (void)hipEventDestroy(s.ev_enc);
-    s = Slot();
+    const bool ok = s.h_arena.reserve(arena) && s.d_in.reserve(arena) && s.d_ws.reserve(std::max<uint64_t>(ws, 256)) &&
+                    s.d_cuts.reserve(ncuts * sizeof(cdc_cut)) && s.h_cuts.reserve(ncuts * sizeof(cdc_cut)) &&
+                    s.d_acuts.reserve(ncuts * sizeof(cdc_cut)) && s.d_dig.reserve(ncuts * 32) &&
+                    s.h_dig.reserve(ncuts * 32) && s.d_hist.reserve(ncuts * 1024) && s.h_hist.reserve(ncuts * 1024) &&
+                    s.d_ent.reserve(ncuts * 8) && s.h_ent.reserve(ncuts * 8) &&
+                    s.d_res.reserve(nfiles * sizeof(cdc_result)) && s.h_res.reserve(nfiles * sizeof(cdc_result)) &&
+                    s.d_meta.reserve(nfiles * 24) && s.h_meta.reserve(nfiles * 24);
+    return ok ? CDC_OK : CDC_E_DEVICE;
 }
 
 }  // namespace
@@ -800,7 +747,7 @@ int enqueue_cuts(Run &R, size_t k)
     for (uint32_t g = 0; g < nf; g += cdc::kMaxBufsPerLaunch) {
         const int m = int(std::min<uint32_t>(cdc::kMaxBufsPerLaunch, nf - g));
         const int st = cdc_chunk_device_batch_async(R.B->device, dp.data() + g, s.lens.data() + g, m, final_, co,
-                                                    cp.data() + g, caps.data() + g, rp.data() + g, s.d_ws, s.ws_cap,
+                                                    cp.data() + g, caps.data() + g, rp.data() + g, s.d_ws, s.d_ws.cap(),
                                                     st1);
         if (st != CDC_OK) {
             cdc::t_force_abort = 0;
@@ -996,7 +943,7 @@ int encode_job(Run &R, EncJob &J, hipStream_t se)
     Slot &s = R.B->slot[J.k % kSlots];
     const uint32_t nb = uint32_t(J.off.size());
     int st;
-    if ((st = grow_dev(s.d_enc, s.enc_cap, J.bound)) != CDC_OK) return st;
+    if (!s.d_enc.reserve(J.bound)) return CDC_E_DEVICE;
     std::vector<uint8_t> rnd;
     if (R.o.key) {
         rnd.resize(56ull * nb);
@@ -1006,14 +953,10 @@ int encode_job(Run &R, EncJob &J, hipStream_t se)
     R.ev("encode", int64_t(J.k), -1, J.bound);
     const auto e0 = Clock::now();
     st = cdc_encode_device(R.B->device, s.d_in, J.off.data(), J.len.data(), nb, R.o.compress, R.o.key,
-                           R.o.key ? rnd.data() : nullptr, s.d_enc, s.enc_cap, oo.data(), se);
+                           R.o.key ? rnd.data() : nullptr, s.d_enc, s.d_enc.cap(), oo.data(), se);
     if (st != CDC_OK) return st;
     const auto e1 = Clock::now();
-    if (oo[nb] > s.henc_cap || !s.h_enc) {
-        const uint64_t want = std::max<uint64_t>(oo[nb], s.enc_cap);
-        if ((st = grow_host(s.h_enc, want, 0)) != CDC_OK) return st;
-        s.henc_cap = want;
-    }
+    if (!s.h_enc.reserve(oo[nb], s.d_enc.cap())) return CDC_E_DEVICE;  // when it grows, to the bound at once
     HIPOK(hipMemcpyAsync(s.h_enc, s.d_enc, oo[nb], hipMemcpyDeviceToHost, se));
     HIPOK(hipStreamSynchronize(se));
     const auto e2 = Clock::now();
@@ -1403,9 +1346,13 @@ void cdc_backup_free(cdc_backup *b)
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);
         }
-    for (auto &s : b->slot) free_slot(s);
+    for (auto &s : b->slot) {
+        for (auto &e : s.ev)
+            if (e) (void)hipEventDestroy(e);
+        if (s.ev_enc) (void)hipEventDestroy(s.ev_enc);
+    }
     for (cdc_packer *p : b->packers) cdc_packer_free(p);
-    delete b;
+    delete b;  // the slots' buffers go with it, the streams drained above
 }
 
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,

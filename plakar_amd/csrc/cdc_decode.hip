@@ -62,6 +62,7 @@
 #include <vector>
 
 #include "cdc_crypto_dev.h"
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "inflate_walk.h"
 #include "lz4_walk.h"
@@ -789,70 +790,22 @@ __global__ __launch_bounds__(256) void k_check_cmp(const uint8_t *got, const uin
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-static std::once_flag g_tab_once;
-static int g_tab_status = CDC_OK;
-
-static int ensure_tables()
-{
-    std::call_once(g_tab_once, [] {
-        uint32_t te0[256];
-        uint8_t sbox[256];
-        enc::build_tables(te0, sbox);
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess) {
-            g_tab_status = CDC_E_DEVICE;
-            return;
-        }
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        for (int d = 0; d < n; ++d) {
-            if (hipSetDevice(d) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_te0), te0, sizeof(te0)) != hipSuccess ||
-                hipMemcpyToSymbol(HIP_SYMBOL(g_sbox), sbox, sizeof(sbox)) != hipSuccess)
-                g_tab_status = CDC_E_DEVICE;
-        }
-        (void)hipSetDevice(cur);
-    });
-    return g_tab_status;
-}
-
-static uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
+static cdc::AesTables g_tab;
 
 // Workspace kept per device between calls (grow-only); a call holds its
 // device's lock while it runs (the entry points are synchronous).
 struct WsCache {
     std::mutex mu;
-    uint8_t *p = nullptr;
-    size_t cap = 0;
-    uint8_t *hp = nullptr;  // pinned staging of the host plan
-    size_t hcap = 0;
-    int cus = 0;
+    cdc::DevBuf ws;
+    cdc::PinBuf stage;  // pinned staging of the host plan
 };
-static WsCache g_ws[64], g_cws[64];
-
-static int ws_reserve(WsCache &C, size_t dev_bytes, size_t host_bytes)
-{
-    if (C.cap < dev_bytes) {
-        if (C.p) (void)hipFree(C.p);
-        C.p = nullptr;
-        C.cap = 0;
-        if (hipMalloc(&C.p, dev_bytes) != hipSuccess) return CDC_E_NOMEM;
-        C.cap = dev_bytes;
-    }
-    if (C.hcap < host_bytes) {
-        if (C.hp) (void)hipHostFree(C.hp);
-        C.hp = nullptr;
-        C.hcap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&C.hp), host_bytes, hipHostMallocDefault) != hipSuccess)
-            return CDC_E_NOMEM;
-        C.hcap = host_bytes;
-    }
-    return CDC_OK;
-}
+// One for Decode and one for the check, per device; never destroyed (DevBuf).
+static WsCache *const g_ws = new WsCache[cdc::kMaxDevices], *const g_cws = new WsCache[cdc::kMaxDevices];
 
 static bool bad_args(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                      const int32_t *status)
 {
-    return device < 0 || device >= 64 || (n && (!d_in || !offsets || !lens || !status));
+    return device < 0 || device >= cdc::kMaxDevices || (n && (!d_in || !offsets || !lens || !status));
 }
 
 // The hashing half of cdc_check_device, over blobs that cdc_decode_device left
@@ -868,40 +821,59 @@ static int check_decoded(int device, const uint8_t *d_scratch, const uint64_t *o
     // ignored.  Empty cuts sit at offset 0, and when nothing decoded at all
     // the hashed buffer is 16 bytes of the workspace, not the caller's.
     const size_t m = n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align16(off + bytes);
-        return o;
-    };
-    const size_t o_cuts = take(m * sizeof(cdc_cut)), o_want = take(m * 32), h_bytes = off;
-    const size_t o_got = take(m * 32), o_diff = take(m * 4), o_dummy = take(16);
+    cdc::Carver cv(16);
+    const size_t o_cuts = cv.take(m * sizeof(cdc_cut)), o_want = cv.take(m * 32), h_bytes = cv.bytes();
+    const size_t o_got = cv.take(m * 32), o_diff = cv.take(m * 4), o_dummy = cv.take(16);
     WsCache &C = g_cws[device];
     std::lock_guard<std::mutex> lk(C.mu);
-    st = ws_reserve(C, off, h_bytes + m * 4);
-    if (st != CDC_OK) return st;
-    cdc_cut *cuts = reinterpret_cast<cdc_cut *>(C.hp + o_cuts);
+    if (!C.ws.reserve(cv.bytes()) || !C.stage.reserve(h_bytes + m * 4)) return CDC_E_NOMEM;
+    uint8_t *const ws = C.ws.as<uint8_t>(), *const hp = C.stage.as<uint8_t>();
+    cdc_cut *cuts = reinterpret_cast<cdc_cut *>(hp + o_cuts);
     for (uint32_t b = 0; b < n; ++b) {
         const uint64_t len = status[b] == CDC_OK ? oo[b + 1] - oo[b] : 0;
         cuts[b] = cdc_cut{len ? oo[b] : 0, uint32_t(len), 0};
     }
-    std::memcpy(C.hp + o_want, checksums, m * 32);
+    std::memcpy(hp + o_want, checksums, m * 32);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemcpyAsync(C.p, C.hp, h_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
-    st = cdc_chunk_digests_device_async(device, oo[n] ? d_scratch : C.p + o_dummy, oo[n],
-                                        reinterpret_cast<const cdc_cut *>(C.p + o_cuts), m, nullptr, C.p + o_got,
+    if (hipMemcpyAsync(ws, hp, h_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
+    st = cdc_chunk_digests_device_async(device, oo[n] ? d_scratch : ws + o_dummy, oo[n],
+                                        reinterpret_cast<const cdc_cut *>(ws + o_cuts), m, nullptr, ws + o_got,
                                         nullptr, stream);
     if (st != CDC_OK) return st;
-    hipLaunchKernelGGL(k_check_cmp, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, s, C.p + o_got, C.p + o_want,
-                       reinterpret_cast<uint32_t *>(C.p + o_diff), uint32_t(m));
-    uint32_t *diff = reinterpret_cast<uint32_t *>(C.hp + h_bytes);
+    hipLaunchKernelGGL(k_check_cmp, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, s, ws + o_got, ws + o_want,
+                       reinterpret_cast<uint32_t *>(ws + o_diff), uint32_t(m));
+    uint32_t *diff = reinterpret_cast<uint32_t *>(hp + h_bytes);
     if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(diff, C.p + o_diff, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(diff, ws + o_diff, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return CDC_E_DEVICE;
     for (uint32_t b = 0; b < n; ++b)
         if (status[b] == CDC_OK && diff[b]) status[b] = CDC_E_MISMATCH;
     return CDC_OK;
+}
+
+// What the host plan takes from one blob's length: its records as the length
+// counts them (nr; a blob that is not CDC_OK opens none of them), its frame
+// bytes and the bytes of its frame slot.
+struct BlobPlan {
+    uint64_t nr, flen, slot;
+    int32_t status;
+};
+static BlobPlan plan_blob(uint64_t len, bool encrypt, int compressed)
+{
+    BlobPlan P{0, len, 0, CDC_OK};
+    if (!encrypt) return P;
+    P.flen = 0;
+    if (len < kHdr) {
+        P.status = CDC_E_CORRUPT;
+        return P;
+    }
+    const uint64_t rem = len - kHdr, nr = (rem + kRecMax - 1) / kRecMax;
+    P.nr = nr;
+    if (nr && rem - (nr - 1) * kRecMax < 28) P.status = CDC_E_CORRUPT;  // a trailing record too short for a nonce and a tag
+    else P.flen = rem - 28 * nr;
+    if (compressed) P.slot = cdc::align_up(rem - std::min<uint64_t>(rem, 28 * nr), 16);
+    return P;
 }
 
 }  // namespace dec
@@ -921,70 +893,49 @@ extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *o
     // plan on the host: records and frame slots follow from the lengths
     uint64_t slot = 0, nrecs = 0;
     for (uint32_t b = 0; b < n; ++b) {
-        if (encrypt && lens[b] >= kHdr) {
-            const uint64_t rem = lens[b] - kHdr, nr = (rem + kRecMax - 1) / kRecMax;
-            nrecs += nr;
-            if (compressed) slot += align16(rem - std::min<uint64_t>(rem, 28 * nr));
-        }
+        const BlobPlan P = plan_blob(lens[b], encrypt, compressed);
+        nrecs += P.nr;
+        slot += P.slot;
     }
     if (nrecs > 0x7FFFFFFFull) return CDC_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
-    int st = ensure_tables();
+    int st = cdc::upload_aes_tables(g_tab, g_te0, g_sbox);
     if (st != CDC_OK) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t nb = n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align16(off + bytes);
-        return o;
-    };
+    cdc::Carver cv(16);
     // the staged prefix (blobs, status, key), then what only the device touches
-    const size_t o_blobs = take(nb * sizeof(DBlob)), o_status = take(nb * 4), o_key = take(32), h_prefix = off;
-    const size_t o_keys = take(encrypt ? nb * sizeof(BlobKey) : 0), o_dsize = take(nb * 8), o_oo = take((nb + 1) * 8);
-    const size_t o_flags = take(16), o_frames = take(encrypt && compressed ? slot : 0);
+    const size_t o_blobs = cv.take(nb * sizeof(DBlob)), o_status = cv.take(nb * 4), o_key = cv.take(32),
+                 h_prefix = cv.bytes();
+    const size_t o_keys = cv.take(encrypt ? nb * sizeof(BlobKey) : 0), o_dsize = cv.take(nb * 8),
+                 o_oo = cv.take((nb + 1) * 8);
+    const size_t o_flags = cv.take(16), o_frames = cv.take(encrypt && compressed ? slot : 0);
     WsCache &C = g_ws[device];
     std::lock_guard<std::mutex> lk(C.mu);
-    st = ws_reserve(C, off, h_prefix);
-    if (st != CDC_OK) return st;
-    if (!C.cus && (hipDeviceGetAttribute(&C.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || C.cus <= 0))
-        C.cus = 256;
-    uint8_t *ws = C.p;
+    if (!C.ws.reserve(cv.bytes()) || !C.stage.reserve(h_prefix)) return CDC_E_NOMEM;
+    const int cus = cdc::device_cus(device);
+    uint8_t *const ws = C.ws.as<uint8_t>(), *const hp = C.stage.as<uint8_t>();
     {
-        DBlob *blobs = reinterpret_cast<DBlob *>(C.hp + o_blobs);
-        int32_t *hst = reinterpret_cast<int32_t *>(C.hp + o_status);
+        DBlob *blobs = reinterpret_cast<DBlob *>(hp + o_blobs);
+        int32_t *hst = reinterpret_cast<int32_t *>(hp + o_status);
         uint64_t sl = 0;
         uint32_t rec = 0;
         for (uint32_t b = 0; b < n; ++b) {
+            const BlobPlan P = plan_blob(lens[b], encrypt, compressed);
             DBlob D{};
             D.src = offsets[b];
             D.len = lens[b];
-            D.flen = lens[b];
+            D.flen = P.flen;
             D.rec0 = rec;
-            hst[b] = CDC_OK;
-            if (encrypt) {
-                D.flen = 0;
-                if (lens[b] < kHdr) {
-                    hst[b] = CDC_E_CORRUPT;
-                } else {
-                    const uint64_t rem = lens[b] - kHdr, nr = (rem + kRecMax - 1) / kRecMax;
-                    if (nr && rem - (nr - 1) * kRecMax < 28) {
-                        hst[b] = CDC_E_CORRUPT;  // a trailing record too short for a nonce and a tag
-                    } else {
-                        D.nrec = uint32_t(nr);
-                        D.flen = rem - 28 * nr;
-                    }
-                    if (compressed) {
-                        D.slot = sl;
-                        sl += align16(rem - std::min<uint64_t>(rem, 28 * nr));
-                    }
-                }
-            }
+            D.nrec = P.status == CDC_OK ? uint32_t(P.nr) : 0u;
+            hst[b] = P.status;
+            if (encrypt && compressed && lens[b] >= kHdr) D.slot = sl;
+            sl += P.slot;
             rec += D.nrec;
             blobs[b] = D;
         }
         nrecs = rec;
-        if (encrypt) std::memcpy(C.hp + o_key, key, 32);
+        if (encrypt) std::memcpy(hp + o_key, key, 32);
     }
     DBatch B{};
     B.in = static_cast<const uint8_t *>(d_in);
@@ -1002,9 +953,9 @@ extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *o
     B.dsize = reinterpret_cast<uint64_t *>(ws + o_dsize);
     B.out_off = reinterpret_cast<uint64_t *>(ws + o_oo);
     B.flags = reinterpret_cast<uint32_t *>(ws + o_flags);
-    const uint32_t open_wgs = uint32_t(std::min<uint64_t>((nrecs + kGcmWaves - 1) / kGcmWaves, uint64_t(C.cus)));
+    const uint32_t open_wgs = uint32_t(std::min<uint64_t>((nrecs + kGcmWaves - 1) / kGcmWaves, uint64_t(cus)));
     const dim3 frame_grid((n + kFrameWaves - 1) / kFrameWaves);
-    bool ok = hipMemcpyAsync(ws, C.hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess &&
+    bool ok = hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess &&
               hipMemsetAsync(ws + o_flags, 0, 16, s) == hipSuccess;
     if (ok) {
         if (encrypt) {
@@ -1041,7 +992,7 @@ extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *o
          hipMemcpyAsync(status, ws + o_status, nb * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
          hipMemcpyAsync(flags, ws + o_flags, 16, hipMemcpyDeviceToHost, s) == hipSuccess &&
          hipStreamSynchronize(s) == hipSuccess;
-    if (encrypt) std::memset(C.hp + o_key, 0, 32);
+    if (encrypt) std::memset(hp + o_key, 0, 32);
     if (!ok) return CDC_E_DEVICE;
     return flags[kFlagNoSpace] ? CDC_E_NOSPACE : CDC_OK;
 }

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 
 namespace cdc {
@@ -605,19 +606,12 @@ thread_local int t_force_abort = 0;
 
 namespace {
 
-uint32_t device_cus()
-{
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-        n = 256;
-    return uint32_t(n);
-}
-
 template <bool kInd>
 int launch_digest_kernels(DigestBatch D, uint64_t cap, bool hist, hipStream_t st, int parts = 3)
 {
-    static const uint32_t cus = device_cus();
+    int dev = -1;  // no current device: the fallback count
+    (void)hipGetDevice(&dev);
+    const uint32_t cus = uint32_t(device_cus(dev));
     // two SHA-256 workgroups per CU (~66 KiB of LDS each)
     D.resident_lanes = g_digest_lanes ? g_digest_lanes : uint64_t(cus) * 2u * 64u * kDigestGroups;
     const uint32_t lanes_per_wg = 64u * kDigestGroups;
@@ -636,7 +630,8 @@ int launch_digest_kernels(DigestBatch D, uint64_t cap, bool hist, hipStream_t st
 constexpr uint32_t kDescRing = 16, kDescMax = 8192;
 struct DescRing {
     std::mutex mu;
-    DigestBuf *h = nullptr, *d = nullptr;
+    PinBuf h;
+    DevBuf d;
     hipEvent_t ev[kDescRing] = {};
     bool used[kDescRing] = {};
     uint32_t next = 0;
@@ -645,8 +640,8 @@ struct DescRing {
 
 DescRing &desc_ring(int device)
 {
-    static DescRing rings[64];
-    return rings[device & 63];
+    static DescRing *rings = new DescRing[kMaxDevices];  // never destroyed (DevBuf)
+    return rings[unsigned(device) % kMaxDevices];
 }
 
 }  // namespace
@@ -732,11 +727,10 @@ int launch_digests_many(const DigestBuf *bufs, uint32_t nbufs, void *stream)
         if (cap == 0) continue;
         if (cap > 0xFFFFFFFFull) return CDC_E_INVALID;
         std::lock_guard<std::mutex> lk(R.mu);
-        if (!R.h) {
-            if (R.failed) return CDC_E_DEVICE;
+        if (R.failed) return CDC_E_DEVICE;
+        if (!R.h.data()) {
             const size_t bytes = size_t(kDescRing) * kDescMax * sizeof(DigestBuf);
-            bool ok = hipHostMalloc(reinterpret_cast<void **>(&R.h), bytes, hipHostMallocDefault) == hipSuccess &&
-                      hipMalloc(reinterpret_cast<void **>(&R.d), bytes) == hipSuccess;
+            bool ok = R.h.reserve(bytes) && R.d.reserve(bytes);
             for (auto &e : R.ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
             if (!ok) {
                 R.failed = true;  // leave it unusable rather than half made
@@ -745,7 +739,7 @@ int launch_digests_many(const DigestBuf *bufs, uint32_t nbufs, void *stream)
         }
         const uint32_t slot = R.next++ % kDescRing;
         if (R.used[slot] && hipEventSynchronize(R.ev[slot]) != hipSuccess) return CDC_E_DEVICE;
-        DigestBuf *h = R.h + size_t(slot) * kDescMax, *d = R.d + size_t(slot) * kDescMax;
+        DigestBuf *h = R.h.as<DigestBuf>() + size_t(slot) * kDescMax, *d = R.d.as<DigestBuf>() + size_t(slot) * kDescMax;
         std::memcpy(h, bufs + i0, n * sizeof(DigestBuf));
         if (hipMemcpyAsync(d, h, n * sizeof(DigestBuf), hipMemcpyHostToDevice, st) != hipSuccess) return CDC_E_DEVICE;
         DigestBatch D;

@@ -59,6 +59,7 @@
 
 #include "cdc_internal.h"
 #include "cdc_crypto_dev.h"
+#include "cdc_hostmem.h"
 #include "deflate_enc.h"
 #include "inflate_walk.h"
 
@@ -1342,62 +1343,28 @@ __global__ __launch_bounds__(64) void k_gz_fin(const Batch B)
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-static std::once_flag g_tab_once;
-static int g_tab_status = CDC_OK;
+static cdc::AesTables g_tab;
 
-static int ensure_tables()
+// The most a blob of len bytes (nblk LZ4 blocks) takes before encryption.
+static uint64_t frame_max(uint64_t len, uint64_t nblk, int compress)
 {
-    std::call_once(g_tab_once, [] {
-        uint32_t te0[256];
-        uint8_t sbox[256];
-        build_tables(te0, sbox);
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess) {
-            g_tab_status = CDC_E_DEVICE;
-            return;
-        }
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        for (int d = 0; d < n; ++d) {
-            if (hipSetDevice(d) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_te0), te0, sizeof(te0)) != hipSuccess ||
-                hipMemcpyToSymbol(HIP_SYMBOL(g_sbox), sbox, sizeof(sbox)) != hipSuccess)
-                g_tab_status = CDC_E_DEVICE;
-        }
-        (void)hipSetDevice(cur);
-    });
-    return g_tab_status;
-}
-
-static uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
-
-// k_gcm's persistent grid: one workgroup per CU (its LDS holds one).
-static uint64_t gcm_wgs()
-{
-    static const uint64_t n = [] {
-        int c = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
-            c = 256;
-        return uint64_t(c);
-    }();
-    return n;
+    return compress == CDC_COMPRESS_GZIP ? dfl::member_bound(len) : compress ? 7 + 4 * nblk + len + 8 : len;
 }
 
 // Workspace kept per device between calls (grow-only); a call holds its
 // device's lock while it runs (the entry point is synchronous).
 struct WsCache {
     std::mutex mu;
-    uint8_t *p = nullptr;
-    size_t cap = 0;
-    uint8_t *hp = nullptr;  // pinned staging of the host plan (one DMA instead of pageable copies)
-    size_t hcap = 0;
+    cdc::DevBuf ws;
+    cdc::PinBuf stage;  // pinned staging of the host plan (one DMA instead of pageable copies)
     hipStream_t aux = nullptr;  // k_xxh32 runs here, beside the LZ4 and GCM kernels
     hipEvent_t fork = nullptr, join = nullptr;
 };
 // Two per device: a caller that runs two Encode calls at once (the backup
 // pipeline's two encoder threads) picks the second with cdc::t_encode_ws = 1,
-// so one call's kernels run beside the other's copy-back.
-static WsCache g_ws[64][2];
+// so one call's kernels run beside the other's copy-back.  Never destroyed
+// (DevBuf).
+static WsCache (*const g_ws)[2] = new WsCache[cdc::kMaxDevices][2];
 
 }  // namespace enc
 
@@ -1413,7 +1380,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                                  uint64_t out_cap, uint64_t *out_offsets, void *stream)
 {
     if ((n && (!d_base || !offsets || !lens || !out_offsets)) || (key && !random) || !d_out) return CDC_E_INVALID;
-    if (device < 0 || device >= 64) return CDC_E_INVALID;
+    if (device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;
     // the selector: 0 none, 2 GZIP, every other value LZ4
     const int mode = compress == CDC_COMPRESS_GZIP ? 2 : compress ? 1 : 0;
     const bool gzip = mode == 2;
@@ -1421,7 +1388,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
         for (uint32_t b = 0; b < n; ++b)
             if (lens[b] > dfl::kMaxBlob) return CDC_E_UNSUPPORTED;  // ISIZE is 32 bits; Decode refuses such a stream
     if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
-    int st = ensure_tables();
+    int st = cdc::upload_aes_tables(g_tab, g_te0, g_sbox);
     if (st != CDC_OK) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool encrypt = key != nullptr;
@@ -1430,47 +1397,35 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     // workspace offsets (no vectors, no copy).
     size_t nk = 0, ng = 0, nsp = 0;
     uint64_t slot = 0, pieces_max = 0;
-    auto frame_max = [&](uint64_t len, uint64_t nblk) {
-        return gzip ? dfl::member_bound(len) : compress ? 7 + 4ull * nblk + len + 8 : len;
-    };
     for (uint32_t b = 0; b < n; ++b) {
         const uint64_t nblk = compress ? (lens[b] + kBlockLZ - 1) / kBlockLZ : 0;
         nk += nblk;
         if (nblk) ng += (nblk - 1) * ((kBlockLZ + kSegLZ - 1) / kSegLZ) +
                         (lens[b] - (nblk - 1) * kBlockLZ + kSegLZ - 1) / kSegLZ;
         if (gzip) nsp += (lens[b] + dfl::kSpan - 1) / dfl::kSpan;
-        const uint64_t fmax = frame_max(lens[b], nblk);
-        slot += align16(fmax);
+        const uint64_t fmax = frame_max(lens[b], nblk, compress);
+        slot += cdc::align_up(fmax, 16);
         pieces_max += encrypt ? (fmax + kPiece - 1) / kPiece : 0;
     }
     // one device allocation for the plan and the workspace
     const size_t nb = n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align16(off + bytes);
-        return o;
-    };
-    const size_t o_blobs = take(nb * sizeof(BlobDesc)), o_blks = take(nk * sizeof(Blk)), o_segs = take(ng * sizeof(Seg));
-    const size_t o_spans = take(nsp * sizeof(Span)), o_bsp = take(gzip ? (nb + 1) * 4 : 0);
-    const size_t o_rnd = take(encrypt ? nb * 56 : 0), o_key = take(32);
-    const size_t o_recs = take(ng * kRecCap * sizeof(uint2)), o_nrec = take(ng * 4), o_trail = take(ng * 4),
-                 o_sout = take(ng * 4);
-    const size_t o_bsz = take(nk * 4), o_bfo = take(nk * 8), o_xxh = take(nb * 4), o_flen = take(nb * 8);
-    const size_t o_oo = take((nb + 1) * 8), o_pb = take((nb + 1) * 4), o_keys = take(encrypt ? nb * sizeof(BlobKey) : 0);
-    const size_t o_status = take(16), o_frames = take(encrypt ? slot : 0), o_xx = take(mode == 1 ? nb * 4 : 0);
-    const size_t o_sp = take(nsp * sizeof(SpanOut)), o_splens = take(nsp * kSpanLens),
-                 o_sphdr = take(nsp * dfl::kHdrWords * 4);
+    cdc::Carver cv(16);
+    const size_t o_blobs = cv.take(nb * sizeof(BlobDesc)), o_blks = cv.take(nk * sizeof(Blk)),
+                 o_segs = cv.take(ng * sizeof(Seg));
+    const size_t o_spans = cv.take(nsp * sizeof(Span)), o_bsp = cv.take(gzip ? (nb + 1) * 4 : 0);
+    const size_t o_rnd = cv.take(encrypt ? nb * 56 : 0), o_key = cv.take(32);
+    const size_t o_recs = cv.take(ng * kRecCap * sizeof(uint2)), o_nrec = cv.take(ng * 4), o_trail = cv.take(ng * 4),
+                 o_sout = cv.take(ng * 4);
+    const size_t o_bsz = cv.take(nk * 4), o_bfo = cv.take(nk * 8), o_xxh = cv.take(nb * 4), o_flen = cv.take(nb * 8);
+    const size_t o_oo = cv.take((nb + 1) * 8), o_pb = cv.take((nb + 1) * 4),
+                 o_keys = cv.take(encrypt ? nb * sizeof(BlobKey) : 0);
+    const size_t o_status = cv.take(16), o_frames = cv.take(encrypt ? slot : 0), o_xx = cv.take(mode == 1 ? nb * 4 : 0);
+    const size_t o_sp = cv.take(nsp * sizeof(SpanOut)), o_splens = cv.take(nsp * kSpanLens),
+                 o_sphdr = cv.take(nsp * dfl::kHdrWords * 4);
     WsCache &C = g_ws[device][cdc::t_encode_ws & 1];
     std::lock_guard<std::mutex> lk(C.mu);
-    if (C.cap < off) {
-        if (C.p) (void)hipFree(C.p);
-        C.p = nullptr;
-        C.cap = 0;
-        if (hipMalloc(&C.p, off) != hipSuccess) return CDC_E_DEVICE;
-        C.cap = off;
-    }
-    uint8_t *ws = C.p;
+    if (!C.ws.reserve(cv.bytes())) return CDC_E_DEVICE;
+    uint8_t *const ws = C.ws.as<uint8_t>();
     if (!C.aux && (hipStreamCreateWithFlags(&C.aux, hipStreamNonBlocking) != hipSuccess ||
                    hipEventCreateWithFlags(&C.fork, hipEventDisableTiming) != hipSuccess ||
                    hipEventCreateWithFlags(&C.join, hipEventDisableTiming) != hipSuccess))
@@ -1478,21 +1433,15 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     // The plan's tables at their workspace offsets [0, o_key + 32) in pinned
     // staging, XXH32 order after them: two DMAs.  (The call ends with a
     // stream sync under C.mu, so the staging is free again on return.)
-    const size_t h_prefix = o_key + 32, h_xx = align16(h_prefix), h_need = h_xx + (mode == 1 ? nb * 4 : 0);
-    if (C.hcap < h_need) {
-        if (C.hp) (void)hipHostFree(C.hp);
-        C.hp = nullptr;
-        C.hcap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&C.hp), h_need, hipHostMallocDefault) != hipSuccess)
-            return CDC_E_NOMEM;
-        C.hcap = h_need;
-    }
+    const size_t h_prefix = o_key + 32, h_xx = cdc::align_up(h_prefix, 16), h_need = h_xx + (mode == 1 ? nb * 4 : 0);
+    if (!C.stage.reserve(h_need)) return CDC_E_NOMEM;
+    uint8_t *const hp = C.stage.as<uint8_t>();
     {
-        BlobDesc *blobs = reinterpret_cast<BlobDesc *>(C.hp + o_blobs);
-        Blk *blks = reinterpret_cast<Blk *>(C.hp + o_blks);
-        Seg *segs = reinterpret_cast<Seg *>(C.hp + o_segs);
-        Span *spans = reinterpret_cast<Span *>(C.hp + o_spans);
-        uint32_t *bsp = reinterpret_cast<uint32_t *>(C.hp + o_bsp);
+        BlobDesc *blobs = reinterpret_cast<BlobDesc *>(hp + o_blobs);
+        Blk *blks = reinterpret_cast<Blk *>(hp + o_blks);
+        Seg *segs = reinterpret_cast<Seg *>(hp + o_segs);
+        Span *spans = reinterpret_cast<Span *>(hp + o_spans);
+        uint32_t *bsp = reinterpret_cast<uint32_t *>(hp + o_bsp);
         uint32_t kb = 0, kg = 0, ks = 0;
         uint64_t sl = 0;
         for (uint32_t b = 0; b < n; ++b) {
@@ -1530,16 +1479,15 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                 }
                 blks[kb++] = K;
             }
-            const uint64_t fmax = frame_max(lens[b], D.nblk);
             D.slot = sl;
-            sl += align16(fmax);
+            sl += cdc::align_up(frame_max(lens[b], D.nblk, compress), 16);
             blobs[b] = D;
         }
         if (gzip) bsp[n] = ks;
         if (kb != nk || kg != ng || ks != nsp) return CDC_E_INVALID;  // the counting pass and the plan disagree (a bug)
         if (encrypt) {
-            std::memcpy(C.hp + o_rnd, random, nb * 56);
-            std::memcpy(C.hp + o_key, key, 32);
+            std::memcpy(hp + o_rnd, random, nb * 56);
+            std::memcpy(hp + o_key, key, 32);
         }
         if (mode == 1 && nb) {
             // XXH32 order: longest first (a wave's blobs end together); ties by
@@ -1550,7 +1498,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
             for (uint32_t b = 0; b < n; ++b)
                 xk[b] = (uint64_t(0xFFFFFFFFu - uint32_t(std::min<uint64_t>(lens[b], 0xFFFFFFFFu))) << 32) | b;
             std::sort(xk.begin(), xk.end());
-            uint32_t *xx = reinterpret_cast<uint32_t *>(C.hp + h_xx);
+            uint32_t *xx = reinterpret_cast<uint32_t *>(hp + h_xx);
             for (size_t i = 0; i < nb; ++i) xx[i] = uint32_t(xk[i]);
         }
     }
@@ -1590,9 +1538,9 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
     Bt.sp_lens = ws + o_splens;
     Bt.sp_hdr = reinterpret_cast<uint32_t *>(ws + o_sphdr);
     const uint32_t xx_wgs = (n + kXxWaves * kXxPerWave - 1) / (kXxWaves * kXxPerWave);
-    bool ok = hipMemcpyAsync(ws, C.hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
+    bool ok = hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
     if (mode == 1 && nb)
-        ok = ok && hipMemcpyAsync(ws + o_xx, C.hp + h_xx, nb * 4, hipMemcpyHostToDevice, s) == hipSuccess;
+        ok = ok && hipMemcpyAsync(ws + o_xx, hp + h_xx, nb * 4, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok && n) {
         if (gzip) {
             if (ng) hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
@@ -1620,7 +1568,10 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
             hipLaunchKernelGGL(k_copy, dim3(n), dim3(256), 0, s, Bt);
         }
         if (encrypt && pieces_max)
-            hipLaunchKernelGGL(k_gcm, dim3(uint32_t(std::min<uint64_t>((pieces_max + kGcmWaves - 1) / kGcmWaves, gcm_wgs()))),
+            // a persistent grid: one workgroup per CU (its LDS holds one)
+            hipLaunchKernelGGL(k_gcm,
+                               dim3(uint32_t(std::min<uint64_t>((pieces_max + kGcmWaves - 1) / kGcmWaves,
+                                                                uint64_t(cdc::device_cus(device))))),
                                dim3(kGcmWaves * 64), 0, s, Bt);
         ok = hipGetLastError() == hipSuccess;
     }
@@ -1640,8 +1591,6 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
 
 extern "C" uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt)
 {
-    const uint64_t f = compress == CDC_COMPRESS_GZIP ? dfl::member_bound(len)
-                       : compress                    ? 7 + 4 * ((len + kBlockLZ - 1) / kBlockLZ) + len + 8
-                                                     : len;
+    const uint64_t f = frame_max(len, (len + kBlockLZ - 1) / kBlockLZ, compress);
     return encrypt ? 60 + f + 28 * ((f + kPiece - 1) / kPiece) : f;
 }

@@ -1,5 +1,6 @@
 // Internal types shared by the HIP kernels (cdc_kernels.hip) and the C-ABI
-// implementation (cdc_api.cpp).  Not part of the public ABI.
+// implementation (cdc_api.cpp).  Not part of the public ABI.  The host-side
+// memory plumbing every stage shares is in cdc_hostmem.h.
 #pragma once
 
 #include <stddef.h>

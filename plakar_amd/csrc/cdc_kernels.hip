@@ -33,6 +33,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 
 namespace cdc {
@@ -2383,8 +2384,6 @@ int launch_stream_read(const void *d_buf, uint64_t len, int reps, double *best_u
 // ---------------------------------------------------------------------------
 // Host side: planning and launching.
 // ---------------------------------------------------------------------------
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 int make_plan(const uint64_t *lens, int nbufs, const DevParams &P, Plan *plan)
 {
     uint64_t maxlen = 0;
@@ -2413,13 +2412,9 @@ int make_plan(const uint64_t *lens, int nbufs, const DevParams &P, Plan *plan)
     // previous pass's resolution).
     uint64_t total = 0;
     for (int i = 0; i < nbufs; ++i) total += lens[i];
-    static const uint64_t cus = [] {
-        int n = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return uint64_t(n);
-    }();
+    int dev = -1;  // no current device: the fallback count
+    (void)hipGetDevice(&dev);
+    const uint64_t cus = uint64_t(device_cus(dev));
     // Persistent scan (CDC_SCAN_TASKS_PER_WAVE = k > 0): one workgroup per CU
     // pulling tasks of 64 lane runs from a counter, about k tasks per wave, so
     // that the CUs that run ahead take the tail.  Measured slower than the
@@ -2469,22 +2464,17 @@ int make_plan(const uint64_t *lens, int nbufs, const DevParams &P, Plan *plan)
     if (segs >= 0xFFFF0000ull || tasks >= 0xFFFF0000ull) return CDC_E_INVALID;
     plan->total_segs = uint32_t(segs);
     plan->total_tasks = uint32_t(tasks);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    plan->off_runs = take(tasks * 64 * 8);
-    plan->off_w1_nodes = take(segs * 64 * 8);
-    plan->off_xg = take(segs * 8);
-    plan->off_sg = take(segs * 8);
-    plan->off_flags = take((kMaxBufsPerLaunch + 4) * 4);  // per buffer + the abort word
+    Carver cv(256);
+    plan->off_runs = cv.take(tasks * 64 * 8);
+    plan->off_w1_nodes = cv.take(segs * 64 * 8);
+    plan->off_xg = cv.take(segs * 8);
+    plan->off_sg = cv.take(segs * 8);
+    plan->off_flags = cv.take((kMaxBufsPerLaunch + 4) * 4);  // per buffer + the abort word
     // [0] segment ticket, [2] persistent scan task counter
-    plan->off_tick = take(16 * 4);
-    plan->off_runsL = take(tasks * 64 * 8);
-    plan->off_validL = take(tasks * 4);
-    plan->bytes = off;
+    plan->off_tick = cv.take(16 * 4);
+    plan->off_runsL = cv.take(tasks * 64 * 8);
+    plan->off_validL = cv.take(tasks * 4);
+    plan->bytes = cv.bytes();
     return CDC_OK;
 }
 

@@ -39,6 +39,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "restore_plan.h"
 
@@ -114,39 +115,15 @@ static void parallel_for(int threads, size_t n, F fn)
     for (auto &x : th) x.join();
 }
 
-static int grow_dev(uint8_t *&p, size_t &cap, size_t need)
-{
-    need = std::max<size_t>(need, 16);
-    if (cap >= need) return CDC_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&p), need) != hipSuccess) return CDC_E_NOMEM;
-    cap = need;
-    return CDC_OK;
-}
-
-static int grow_pin(uint8_t *&p, size_t &cap, size_t need)
-{
-    need = std::max<size_t>(need, 16);
-    if (cap >= need) return CDC_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipHostMalloc(reinterpret_cast<void **>(&p), need, hipHostMallocDefault) != hipSuccess) return CDC_E_NOMEM;
-    cap = need;
-    return CDC_OK;
-}
-
 struct InSlot {   // reader -> device stage
-    uint8_t *h = nullptr, *d = nullptr;
-    size_t hcap = 0, dcap = 0;
+    cdc::PinBuf h;
+    cdc::DevBuf d;
     std::vector<uint64_t> eoff, elen;  // the batch's encoded blobs in the arena
     std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
 };
 struct OutSlot {  // device stage -> writer
-    uint8_t *d = nullptr, *h = nullptr;
-    size_t dcap = 0, hcap = 0;
+    cdc::DevBuf d;
+    cdc::PinBuf h;
 };
 
 }  // namespace
@@ -162,8 +139,7 @@ struct cdc_restore {
     hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stages, download
     InSlot in[2];
     OutSlot out[2];
-    uint8_t *plain = nullptr;
-    size_t plain_cap = 0;
+    cdc::DevBuf plain;
     std::mutex run_mu;
 };
 
@@ -259,29 +235,28 @@ static void reader_stage(Run &X)
             const Pack &P = R->packs[L.pack];
             if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
         }
-        int st = grow_pin(S.h, S.hcap, total);
-        if (st == CDC_OK) st = grow_dev(S.d, S.dcap, total);
-        if (st != CDC_OK) {
+        if (!S.h.reserve(total) || !S.d.reserve(total)) {
             for (auto &f : fds)
                 if (f.second >= 0) close(f.second);
-            return X.abort_run(st);
+            return X.abort_run(CDC_E_NOMEM);
         }
+        uint8_t *const h = S.h.as<uint8_t>();
         parallel_for(R->o.writers, nb, [&](size_t b) {
             const Loc &L = R->locs[B.blobs[b].id];
             const Pack &P = R->packs[L.pack];
             if (P.mem) {
-                std::memcpy(S.h + S.eoff[b], P.mem + L.offset, L.length);
+                std::memcpy(h + S.eoff[b], P.mem + L.offset, L.length);
                 return;
             }
             const int fd = fds.find(L.pack)->second;
-            if (fd < 0 || !pread_all(fd, S.h + S.eoff[b], L.length, L.offset)) S.pre[b] = CDC_E_IO;
+            if (fd < 0 || !pread_all(fd, h + S.eoff[b], L.length, L.offset)) S.pre[b] = CDC_E_IO;
         });
         for (auto &f : fds)
             if (f.second >= 0) close(f.second);
         X.read_s += since(t0);
         X.st.encoded_bytes += total;
         t0 = Clock::now();
-        if (total && (hipMemcpyAsync(S.d, S.h, total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
+        if (total && (hipMemcpyAsync(S.d.data(), h, total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
                       hipStreamSynchronize(R->stream[0]) != hipSuccess))
             return X.abort_run(CDC_E_DEVICE);
         X.h2d_s += since(t0);
@@ -302,11 +277,11 @@ static void device_stage(Run &X)
         InSlot &I = R->in[k & 1];
         OutSlot &O = R->out[k & 1];
         const uint32_t nb = uint32_t(B.blobs.size());
-        int st = grow_dev(O.d, O.dcap, B.out_bytes);
-        if (st == CDC_OK) st = grow_pin(O.h, O.hcap, B.out_bytes);
         bool direct = B.identity;  // decode straight into the output image
-        if (st == CDC_OK && !direct) st = grow_dev(R->plain, R->plain_cap, B.plain_bytes);
-        if (st != CDC_OK) return X.abort_run(st);
+        if (!O.d.reserve(B.out_bytes) || !O.h.reserve(B.out_bytes) || (!direct && !R->plain.reserve(B.plain_bytes)))
+            return X.abort_run(CDC_E_NOMEM);
+        uint8_t *const out = O.d.as<uint8_t>();
+        int st;
         oo.assign(size_t(nb) + 1, 0);
         bst.assign(std::max<uint32_t>(nb, 1), CDC_OK);
         if (R->o.verify) {
@@ -317,8 +292,8 @@ static void device_stage(Run &X)
             if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
         const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
         const uint8_t *sums = R->o.verify ? want.data() : nullptr;
-        st = cdc::decode_checked(R->device, I.d, I.eoff.data(), I.elen.data(), nb, R->o.compress, key, sums,
-                                 direct ? O.d : R->plain, B.plain_bytes, oo.data(), bst.data(), R->stream[1],
+        st = cdc::decode_checked(R->device, I.d.data(), I.eoff.data(), I.elen.data(), nb, R->o.compress, key, sums,
+                                 direct ? out : R->plain.as<uint8_t>(), B.plain_bytes, oo.data(), bst.data(), R->stream[1],
                                  &X.decode_s, &X.verify_s);
         pos.assign(oo.begin(), oo.end() - 1);
         uint64_t plain_used = oo[nb];
@@ -329,11 +304,11 @@ static void device_stage(Run &X)
             // out, the others are the mismatch.  (A slow path: it runs only
             // for a batch that holds such a blob.)
             direct = false;
-            st = grow_dev(R->plain, R->plain_cap, B.plain_bytes);
+            st = R->plain.reserve(B.plain_bytes) ? CDC_OK : CDC_E_NOMEM;
             for (uint32_t b = 0; b < nb && st == CDC_OK; ++b) {
                 uint64_t o2[2] = {0, 0};
-                st = cdc::decode_checked(R->device, I.d, &I.eoff[b], &I.elen[b], 1, R->o.compress, key,
-                                         sums ? sums + size_t(b) * 32 : nullptr, R->plain + B.blobs[b].off,
+                st = cdc::decode_checked(R->device, I.d.data(), &I.eoff[b], &I.elen[b], 1, R->o.compress, key,
+                                         sums ? sums + size_t(b) * 32 : nullptr, R->plain.as<uint8_t>() + B.blobs[b].off,
                                          B.blobs[b].len, o2, &bst[b], R->stream[1], &X.decode_s, &X.verify_s);
                 if (st == CDC_E_NOSPACE) {
                     st = CDC_OK;
@@ -370,10 +345,9 @@ static void device_stage(Run &X)
             const auto t0 = Clock::now();
             bool ok = true;
             if (direct) {  // the plaintext sits compacted in the image: move it out of the way first
-                st = grow_dev(R->plain, R->plain_cap, plain_used);
-                if (st != CDC_OK) return X.abort_run(st);
+                if (!R->plain.reserve(plain_used)) return X.abort_run(CDC_E_NOMEM);
                 ok = !plain_used ||
-                     hipMemcpyAsync(R->plain, O.d, plain_used, hipMemcpyDeviceToDevice, R->stream[1]) == hipSuccess;
+                     hipMemcpyAsync(R->plain.data(), out, plain_used, hipMemcpyDeviceToDevice, R->stream[1]) == hipSuccess;
             }
             so.clear();
             sl.clear();
@@ -385,7 +359,7 @@ static void device_stage(Run &X)
                 sd.push_back(S.dst_off);
             }
             if (ok && !so.empty())
-                st = cdc_assemble_device(R->device, R->plain, plain_used, so.data(), sl.data(), sd.data(), so.size(), O.d,
+                st = cdc_assemble_device(R->device, R->plain.data(), plain_used, so.data(), sl.data(), sd.data(), so.size(), out,
                                          B.out_bytes, R->stream[1]);
             if (st != CDC_OK) return X.abort_run(st);
             if (!ok || hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
@@ -416,13 +390,14 @@ static void writer_stage(Run &X)
         if (!X.wait_for(X.assembled, k + 1)) return;
         const rplan::Batch &B = X.batches[k];
         OutSlot &O = R->out[k & 1];
+        uint8_t *const image = O.h.as<uint8_t>();
         auto t0 = Clock::now();
-        if (B.out_bytes && (hipMemcpyAsync(O.h, O.d, B.out_bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
+        if (B.out_bytes && (hipMemcpyAsync(image, O.d.data(), B.out_bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
                             hipStreamSynchronize(R->stream[2]) != hipSuccess))
             return X.abort_run(CDC_E_DEVICE);
         X.d2h_s += since(t0);
         t0 = Clock::now();
-        parallel_for(R->o.writers, B.pieces.size(), [&](size_t i) { write_piece(X, B.pieces[i], O.h); });
+        parallel_for(R->o.writers, B.pieces.size(), [&](size_t i) { write_piece(X, B.pieces[i], image); });
         X.write_s += since(t0);
         for (const rplan::Piece &P : B.pieces) {
             const int fi = X.pidx[P.file];
@@ -439,7 +414,7 @@ static void writer_stage(Run &X)
                 }
             } else {
                 if (P.last) X.reported[fi] = 1;
-                X.report(fi, s, X.fseen[fi]++, X.fpieces[fi], s == CDC_OK ? O.h + P.dst_off : nullptr, P.file_off,
+                X.report(fi, s, X.fseen[fi]++, X.fpieces[fi], s == CDC_OK ? image + P.dst_off : nullptr, P.file_off,
                          s == CDC_OK ? P.len : 0);
             }
         }
@@ -584,7 +559,7 @@ int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out)
 {
     if (!opts || !out) return CDC_E_INVALID;
     *out = nullptr;
-    if (device < 0 || device >= 64 || opts->writers < 0 || opts->writers > 256) return CDC_E_INVALID;
+    if (device < 0 || device >= cdc::kMaxDevices || opts->writers < 0 || opts->writers > 256) return CDC_E_INVALID;
     if (!cdc::device_count_initialised()) return CDC_E_NOT_INIT;
     auto *r = new (std::nothrow) cdc_restore();
     if (!r) return CDC_E_NOMEM;
@@ -683,17 +658,8 @@ void cdc_restore_free(cdc_restore *r)
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);
         }
-    for (InSlot &s : r->in) {
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-    }
-    for (OutSlot &s : r->out) {
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-    }
-    if (r->plain) (void)hipFree(r->plain);
     if (!r->key.empty()) std::memset(r->key.data(), 0, r->key.size());
-    delete r;
+    delete r;  // the slots' buffers and `plain` go with it, the streams drained above
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "cdc_hostmem.h"
 #include "cdc_internal.h"
 
 namespace asmb {
@@ -117,8 +118,8 @@ __global__ __launch_bounds__(kThreads) void k_assemble(const Job J)
 // pairs per device, so the call stays asynchronous: a slot is reused only once
 // the launch that read it has finished (its event).
 struct TabSlot {
-    uint64_t *h = nullptr, *d = nullptr;
-    size_t cap = 0;  // rows
+    cdc::PinBuf h;
+    cdc::DevBuf d;
     hipEvent_t ev = nullptr;
     bool used = false;
 };
@@ -126,27 +127,19 @@ struct TabRing {
     std::mutex mu;
     TabSlot s[4];
     unsigned next = 0;
-    int cus = 0;
 };
-static TabRing g_ring[64];
+static TabRing *const g_ring = new TabRing[cdc::kMaxDevices];  // never destroyed (DevBuf)
 static std::atomic<int> g_policy{2};
 
+// The slot once its last launch is done, with room for `rows` rows of 24 bytes
+// (it grows by half again, from 1,024 rows).
 static int slot_reserve(TabSlot &S, size_t rows)
 {
     if (!S.ev && hipEventCreateWithFlags(&S.ev, hipEventDisableTiming) != hipSuccess) return CDC_E_DEVICE;
     if (S.used && hipEventSynchronize(S.ev) != hipSuccess) return CDC_E_DEVICE;
     S.used = false;
-    if (S.cap >= rows) return CDC_OK;
-    if (S.h) (void)hipHostFree(S.h);
-    if (S.d) (void)hipFree(S.d);
-    S.h = S.d = nullptr;
-    S.cap = 0;
     const size_t want = std::max<size_t>(rows + rows / 2, 1024);
-    if (hipHostMalloc(reinterpret_cast<void **>(&S.h), want * 24, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&S.d), want * 24) != hipSuccess)
-        return CDC_E_NOMEM;
-    S.cap = want;
-    return CDC_OK;
+    return S.h.reserve(rows * 24, want * 24) && S.d.reserve(rows * 24, want * 24) ? CDC_OK : CDC_E_NOMEM;
 }
 
 }  // namespace asmb
@@ -164,7 +157,7 @@ extern "C" int cdc_assemble_device(int device, const void *d_src, uint64_t src_c
                                    const uint64_t *len, const uint64_t *dst_off, uint64_t n, void *d_dst,
                                    uint64_t dst_cap, void *stream)
 {
-    if (device < 0 || device >= 64 || (n && (!src_off || !len || !dst_off))) return CDC_E_INVALID;
+    if (device < 0 || device >= cdc::kMaxDevices || (n && (!src_off || !len || !dst_off))) return CDC_E_INVALID;
     uint64_t rows = 0, end = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (len[i] > src_cap || src_off[i] > src_cap - len[i]) return CDC_E_INVALID;
@@ -184,33 +177,32 @@ extern "C" int cdc_assemble_device(int device, const void *d_src, uint64_t src_c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     TabRing &R = g_ring[device];
     std::lock_guard<std::mutex> lk(R.mu);
-    if (!R.cus && (hipDeviceGetAttribute(&R.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || R.cus <= 0))
-        R.cus = 256;
     TabSlot &S = R.s[R.next++ % 4];
     int st = slot_reserve(S, rows);
     if (st != CDC_OK) return st;
+    uint64_t *const h = S.h.as<uint64_t>(), *const d = S.d.as<uint64_t>();
     uint64_t k = 0, first = 0, last = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (!len[i]) continue;
         if (!k) first = dst_off[i];
         last = dst_off[i] + len[i];
-        S.h[k] = dst_off[i];
-        S.h[rows + k] = src_off[i];
-        S.h[2 * rows + k] = len[i];
+        h[k] = dst_off[i];
+        h[rows + k] = src_off[i];
+        h[2 * rows + k] = len[i];
         ++k;
     }
     Job J{};
     J.mis = reinterpret_cast<uintptr_t>(d_dst) & 15;
     J.src = static_cast<const uint8_t *>(d_src);
     J.dst16 = static_cast<uint8_t *>(d_dst) - J.mis;
-    J.dst_off = S.d;
-    J.src_off = S.d + rows;
-    J.len = S.d + 2 * rows;
+    J.dst_off = d;
+    J.src_off = d + rows;
+    J.len = d + 2 * rows;
     J.n = rows;
     J.tile0 = (first + J.mis) / kTile;
     J.ntiles = (last + J.mis - 1) / kTile - J.tile0 + 1;
-    const uint32_t grid = uint32_t(std::min<uint64_t>(J.ntiles, uint64_t(R.cus) * kBlocksPerCU));
-    if (hipMemcpyAsync(S.d, S.h, rows * 24, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
+    const uint32_t grid = uint32_t(std::min<uint64_t>(J.ntiles, uint64_t(cdc::device_cus(device)) * kBlocksPerCU));
+    if (hipMemcpyAsync(d, h, rows * 24, hipMemcpyHostToDevice, s) != hipSuccess) return CDC_E_DEVICE;
     switch (g_policy.load(std::memory_order_relaxed)) {
     case 0: hipLaunchKernelGGL(k_assemble<0>, dim3(grid), dim3(kThreads), 0, s, J); break;
     case 1: hipLaunchKernelGGL(k_assemble<1>, dim3(grid), dim3(kThreads), 0, s, J); break;
