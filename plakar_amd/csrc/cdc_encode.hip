@@ -1166,9 +1166,6 @@ __device__ __forceinline__ dfl::SpanView span_view(const Batch &B, const Span &S
     return V;
 }
 
-// x^(8 bytes) mod P for crc_mul (the polynomial is primitive: exponents count mod 2^32 - 1).
-__device__ __forceinline__ uint32_t crc_shift(uint64_t bytes) { return infw::crc_xpow(uint32_t(8 * bytes % 0xFFFFFFFFull)); }
-
 struct alignas(16) DflSizeLds {
     uint32_t data[dfl::kSpan / 4];
     uint32_t lfreq[dfl::kLitSlots], dfreq[dfl::kDistSlots];
@@ -1207,7 +1204,7 @@ __global__ __launch_bounds__(kDflThreads) void k_dfl_size(const Batch B)
         const uint32_t a = min(t * dfl::kStretch, S.len), e = min(a + dfl::kStretch, S.len);
         uint32_t r = 0;
         for (uint32_t i = a; i < e; ++i) r = infw::crc_bits(r, rd(i));
-        if (r) r = infw::crc_mul(r, crc_shift(S.len - e));
+        if (r) r = infw::crc_mul(r, infw::crc_shift(S.len - e));
         for (int o = 32; o; o >>= 1) r ^= __shfl_xor(r, o);
         if ((t & 63u) == 0) L.crc[t >> 6] = r;
     }
@@ -1322,13 +1319,13 @@ __global__ __launch_bounds__(64) void k_gz_fin(const Batch B)
     for (uint32_t k = lane; k < n; k += 64) {
         const SpanOut &o = B.sp[s0 + k];
         const uint64_t done = min<uint64_t>(len, uint64_t(k + 1) * dfl::kSpan);
-        acc ^= infw::crc_mul(o.crc, crc_shift(len - done));
+        acc ^= infw::crc_mul(o.crc, infw::crc_shift(len - done));
         if (k && (o.bit & 7u)) f[o.bit >> 3] = uint8_t(B.sp[s0 + k - 1].edge_hi | o.edge_lo);
     }
     for (int o = 32; o; o >>= 1) acc ^= __shfl_xor(acc, o);
     if (lane == 0) {
         // the register started from 0xFFFFFFFF, not 0: that start moved past len bytes
-        const uint32_t crc = ~(acc ^ infw::crc_mul(0xFFFFFFFFu, crc_shift(len)));
+        const uint32_t crc = ~(acc ^ infw::crc_mul(0xFFFFFFFFu, infw::crc_shift(len)));
         const SpanOut &o = B.sp[s0 + n - 1];
         const uint64_t E = o.bit + o.nbits;
         if (E & 7u) f[E >> 3] = uint8_t(o.edge_hi);

@@ -117,6 +117,9 @@ INFW_HD uint32_t crc_xpow(uint32_t e)
     return r;
 }
 
+// x^(8 bytes) mod P for crc_mul (the polynomial is primitive: exponents count mod 2^32 - 1).
+INFW_HD uint32_t crc_shift(uint64_t bytes) { return crc_xpow(uint32_t(8 * bytes % 0xFFFFFFFFull)); }
+
 // The lanes' slices: the n bytes, with 64 S - n zero bytes imagined before
 // them, are cut into 64 slices of S bytes.  A register of 0 passes leading
 // zeros unchanged, so the slice that holds byte 0 starts from 0xFFFFFFFF there

@@ -20,6 +20,14 @@
 //    and a line
 //      M <name> <member bytes> <content bytes> <stored> <fixed> <dynamic>
 //    counts its blocks by kind.
+// 3. The member's CRC-32 as the device assembles it, restated serially with the
+//    shared functions (inflate_walk.h: crc_bits, crc_mul, crc_shift): a register
+//    from zero over every 128-byte stretch, moved to its span's end; the spans'
+//    registers moved to the member's end; the 0xFFFFFFFF start moved past the
+//    whole length; the complement.  Against zlib's crc32 over random contents:
+//      C <bytes> <crc32 in hex>
+//    and the shift alone over 2^29 + 3 zero bytes, where 8 * bytes passes 2^32:
+//      S <bytes> <crc32 in hex>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +38,7 @@
 #include <vector>
 
 #include "../../plakar_amd/csrc/deflate_enc.h"
+#include "../../plakar_amd/csrc/inflate_walk.h"
 
 #if __has_include(<zlib.h>)
 #include <zlib.h>
@@ -439,6 +448,60 @@ static void member_cases(FILE *out)
     }
 }
 
+// ---- 3. the CRC-32's assembly ----------------------------------------------------------
+// What k_dfl_size (stretches into a span's register) and k_gz_fin (spans into
+// the member's CRC-32) compute, one term after the other.
+static uint32_t assembled_crc(const uint8_t *p, uint64_t len)
+{
+    using namespace dfl;
+    uint32_t acc = 0;
+    const uint64_t nspan = (len + kSpan - 1) / kSpan;
+    for (uint64_t k = 0; k < nspan; ++k) {
+        const uint64_t s0 = k * kSpan, done = len < s0 + kSpan ? len : s0 + kSpan;
+        const uint32_t slen = uint32_t(done - s0);
+        uint32_t span = 0;
+        for (uint32_t a = 0; a < slen; a += kStretch) {
+            const uint32_t e = a + kStretch < slen ? a + kStretch : slen;
+            uint32_t r = 0;
+            for (uint32_t i = a; i < e; ++i) r = infw::crc_bits(r, p[s0 + i]);
+            if (r) r = infw::crc_mul(r, infw::crc_shift(slen - e));
+            span ^= r;
+        }
+        acc ^= infw::crc_mul(span, infw::crc_shift(len - done));
+    }
+    return ~(acc ^ infw::crc_mul(0xFFFFFFFFu, infw::crc_shift(len)));
+}
+
+static void crc_cases()
+{
+    for (uint64_t n : {1ull, 127ull, 128ull, 129ull, 32767ull, 32768ull, 32769ull, (2ull << 20) + 1, (4ull << 20) + 5,
+                       (8ull << 20) + 3}) {
+        std::unique_ptr<uint8_t[]> data(new uint8_t[n]);  // exactly sized: a read past it is a report
+        for (uint64_t i = 0; i < n; ++i) data[i] = uint8_t(rnd());
+        const uint32_t want = uint32_t(crc32(0, data.get(), unsigned(n))), got = assembled_crc(data.get(), n);
+        CHECK(got == want, "CRC-32 of %llu bytes: assembled %08x, zlib %08x", (unsigned long long)n, got, want);
+        printf("C %llu %08x\n", (unsigned long long)n, got);
+    }
+    // the shift alone: a register moved past 2^29 + 3 zero bytes (8 * bytes = 2^32 + 24: the
+    // exponent is reduced mod 2^32 - 1, not cut to 32 bits); zlib is fed the zeros 1 MiB at a time
+    const uint64_t zeros = (1ull << 29) + 3;
+    CHECK(8 * zeros > 0xFFFFFFFFull, "the exponent passes 2^32");
+    const uint8_t head[5] = {'s', 'h', 'i', 'f', 't'};
+    unsigned long z = crc32(0, head, 5);
+    const uint32_t got = ~infw::crc_mul(~uint32_t(z), infw::crc_shift(zeros));  // zlib keeps the register complemented
+    std::unique_ptr<uint8_t[]> mib(new uint8_t[1 << 20]());
+    for (uint64_t left = zeros; left;) {
+        const unsigned k = unsigned(left < (1u << 20) ? left : (1u << 20));
+        z = crc32(z, mib.get(), k);
+        left -= k;
+    }
+    CHECK(got == uint32_t(z), "a register moved past %llu zero bytes: %08x, zlib %08x", (unsigned long long)zeros, got,
+          uint32_t(z));
+    CHECK(infw::crc_shift(zeros) == infw::crc_xpow(25) && infw::crc_shift(zeros) != infw::crc_xpow(24),
+          "x^(2^32 + 24) is x^25 mod P, not x^24");
+    printf("S %llu %08x\n", (unsigned long long)zeros, got);
+}
+
 int main(int argc, char **argv)
 {
     FILE *out = nullptr;
@@ -475,6 +538,7 @@ int main(int argc, char **argv)
     histogram_cases();
     member_cases(out);
     if (out) fclose(out);
+    crc_cases();
     if (g_fail) {
         printf("%d checks failed\n", g_fail);
         return 1;

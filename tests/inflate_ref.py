@@ -126,7 +126,9 @@ def inflate(data, start=0, omax=None):
     """The DEFLATE stream at data[start:]: (output, index after the last block,
     walk).  walk: per block a dict(btype, first (output index), matches [(pos,
     length, distance)], maxbits, cl (the code-length symbols read), nlit,
-    ndist, litlens, distlens).  Raises Corrupt."""
+    ndist, litlens, distlens, and bit0 / bit1: the bit of data (counted from
+    its byte 0) at which the block's BFINAL stands, and the one after the
+    block's last bit, a stored block's last byte included).  Raises Corrupt."""
     global _FIXED
     if _FIXED is None:
         _FIXED = (_table(FIXED_LIT), _table(FIXED_DIST))
@@ -134,8 +136,9 @@ def inflate(data, start=0, omax=None):
     out = bytearray()
     walk = []
     while True:
+        bit0 = 8 * B.pos - B.cnt
         final, btype = B.bit(), B.bits(2)
-        blk = dict(btype=btype, first=len(out), matches=[], maxbits=0, cl=[], stored=None)
+        blk = dict(btype=btype, first=len(out), matches=[], maxbits=0, cl=[], stored=None, bit0=bit0, bit1=None)
         walk.append(blk)
         if btype == 3:
             raise Corrupt("BTYPE 3")
@@ -219,6 +222,7 @@ def inflate(data, start=0, omax=None):
                 else:
                     for _ in range(ln):
                         out.append(out[-ds])
+        blk["bit1"] = 8 * B.pos - B.cnt
         if final:
             break
     return bytes(out), B.align(), walk

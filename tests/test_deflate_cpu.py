@@ -1,7 +1,8 @@
 """GZIP Encode's checks that need no GPU: the shared DEFLATE writer
 (plakar_amd/csrc/deflate_enc.h) passes the sanitizer program (code lengths
 from seeded histograms, whole members from hand-made record lists, each judged
-by zlib there and by inflate_ref here), the bound, the entry point's argument
+by zlib there and by inflate_ref here, and the CRC-32 assembled from stretches
+and spans as the device does it, against zlib's), the bound, the entry point's argument
 checks before the device, the Python layers, and the compiler's resource
 report of the new kernels."""
 import ctypes
@@ -100,6 +101,25 @@ def test_members_written_on_the_host_inflate(run):
     m, c = name_to["alternating"]
     _, _, walk = ir.inflate(m, 10)
     assert [b["btype"] for b in walk[:4]] == [2, 0, 2, 0]
+
+
+def test_crc32_assembly_equals_zlib(run):
+    """The program restated the device's CRC-32 assembly (stretches, spans,
+    the moved start) with the shared functions and compared it with zlib's
+    crc32 itself; here: it printed every size, and the shift past 2^29 + 3
+    zero bytes, where the exponent is reduced mod 2^32 - 1."""
+    stdout, _ = run
+    rows = re.findall(r"^C (\d+) ([0-9a-f]{8})$", stdout, re.M)
+    assert [int(n) for n, _ in rows] == [1, 127, 128, 129, 32767, 32768, 32769, (2 << 20) + 1, (4 << 20) + 5,
+                                         (8 << 20) + 3]
+    assert len({c for _, c in rows}) == len(rows)
+    (shift,) = re.findall(r"^S (\d+) ([0-9a-f]{8})$", stdout, re.M)
+    n = (1 << 29) + 3
+    assert int(shift[0]) == n and 8 * n > 1 << 32
+    z, piece = zlib.crc32(b"shift"), bytes(1 << 20)
+    for _ in range(n >> 20):
+        z = zlib.crc32(piece, z)
+    assert int(shift[1], 16) == zlib.crc32(bytes(n & 0xFFFFF), z)
 
 
 @pytest.mark.parametrize("n", [0, 1, 65535, 65536, 65537, (4 << 20) + 5])

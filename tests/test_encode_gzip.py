@@ -1,6 +1,7 @@
 """GZIP Encode on the device (cdc_encode_device with compress =
 CDC_COMPRESS_GZIP) against zlib and inflate_ref: every inflater reads the
-members, the three block forms occur where they should, the ratio conditions,
+members, stored and dynamic blocks occur where they should (the fixed form and
+the choice between the three: test_encode_gzip_large.py), the ratio conditions,
 the bound and the space check, Decode and the blob check read them back on the
 device, and the backup pipeline writes a GZIP repository that Restore reads."""
 import functools
