@@ -256,6 +256,77 @@ int cdc_check_device(int device, const void *d_in, const uint64_t *offsets, cons
                      int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_scratch,
                      uint64_t scratch_cap, uint64_t *needed, int32_t *status, void *stream);
 
+/* ---- Transcode: a blob of one repository as a blob of another ---------------------
+ * What `plakar sync` does to every blob the destination lacks (synchronize,
+ * cmd/plakar/subcommands/sync/sync.go:182-266): GetBlob decodes it with the
+ * source repository's compression and key (repository/repository.go:186-210,
+ * 407-429), PutBlob encodes it with the destination's (repository.go:212-236,
+ * snapshot/blobs.go:9-24).  A codec is one side's configuration: the
+ * compression selector above and the 32-byte repository key (host memory), or
+ * NULL when that side is not encrypted. */
+typedef struct cdc_codec {
+    int compress;        /* CDC_COMPRESS_NONE, _LZ4 or _GZIP */
+    const uint8_t *key;  /* 32 bytes, or NULL */
+} cdc_codec;
+
+/* The exact stored length after a transcode that keeps the compression (the
+ * same selector on both sides) of a blob of `len` stored bytes: the GCM
+ * envelope of encryption.EncryptStream (encryption/symmetric.go:72-163) taken
+ * off, put on, or exchanged (then the length stays).  CDC_E_CORRUPT for a
+ * length no writer produces (an encrypted source under 60 bytes, or with a
+ * trailing record under 28, as cdc_decode_device).  Host only; needs no
+ * cdc_init. */
+int64_t cdc_transcode_size(uint64_t len, int src_encrypted, int dst_encrypted);
+
+/* synchronize's GetBlob + PutBlob (sync.go:182-266) for n stored blobs that sit
+ * in device memory at d_in + offsets[i], lens[i] bytes each.  The host decides
+ * the path from the two codecs:
+ *   same compression, both keys: the re-key.  Only the envelope changes (the
+ *     sealed subkey, the nonces, the ciphertext and the tags); the compressed
+ *     bytes inside it are carried over, and the plaintext never exists in
+ *     device memory: one kernel authenticates each record under the source
+ *     subkey (every tag compared in full: CDC_E_AUTH), exchanges the two
+ *     keystreams in registers and seals it under the destination's.  Output
+ *     length = input length; record k of a blob carries the blob's data nonce
+ *     with its last four bytes XOR k, as cdc_encode_device writes it.
+ *   same compression, only the source key: cdc_decode_device with compressed = 0.
+ *   same compression, only the destination key: cdc_encode_device with
+ *     compress = 0 over the stored bytes.
+ *   same compression, no key: a copy.
+ *   different compression: cdc_decode_device into a workspace the library keeps
+ *     per device, then cdc_encode_device from there, over the blobs that
+ *     decoded only (a failed blob is never encoded as an empty one).  The
+ *     plaintext stays on the device.
+ * checksums (host, 32 bytes per blob, or NULL): when given, every blob is
+ * first checked as cdc_check_device does (decoded into the workspace, SHA-256,
+ * compared); one that fails gets its decode error or CDC_E_MISMATCH and is
+ * left out of the path that follows.  Without checksums the same-compression
+ * paths trust the envelope and do not inflate: an encrypted source is
+ * authenticated by its tags, an unencrypted one is copied unvalidated.  The
+ * reference always inflates in GetBlob, so a caller who wants to be at least
+ * as strict passes the index checksums.
+ * random (host, 56 bytes per blob of the batch, as cdc_encode_device: subkey
+ * 32, subkey nonce 12, data nonce 12) is needed when dst->key is set; row i
+ * belongs to blob i whether or not other blobs fail.
+ * Blob i's new encoding lands at d_out + out_offsets[i] (host array of n + 1,
+ * out_offsets[n] = total), packed without padding.  Returns CDC_OK whenever
+ * the batch ran: status[i] (host, n) is CDC_OK or blob i's error, and a failed
+ * blob contributes 0 bytes.  CDC_E_NOSPACE comes with out_offsets[n] = the
+ * capacity needed and nothing written (d_out may be NULL when out_cap is 0);
+ * on the re-key path that is the sum of the well-formed blobs' lengths.
+ * d_out[out_offsets[n], out_cap) is scratch for the call, as for
+ * cdc_decode_device: a blob whose tag fails is found out after its planned
+ * range was (partly) written, the blobs after it are then moved down over it,
+ * and the bytes between the final out_offsets[n] and the total planned before
+ * are left overwritten.  [d_in, ...) and [d_out, + out_cap) must not overlap.
+ * CDC_E_INVALID: a NULL argument, a device outside 0..63, dst->key without
+ * random, or a batch of more than 2^31 - 1 GCM records; CDC_E_NOT_INIT before
+ * cdc_init.  Every read stays inside its blob and every write inside
+ * d_out[0, out_cap).  Synchronous on `stream`. */
+int cdc_transcode_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                         const cdc_codec *src, const cdc_codec *dst, const uint8_t *checksums, const uint8_t *random,
+                         uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets, int32_t *status, void *stream);
+
 /* ---- packfile builder: the consumer of the cut lists ---------------------------
  * snapshot/packer.go + packfile/packfile.go: blobs are appended to a
  * packfile whose bytes are those of (*PackFile).Serialize (packfile.go:241-294):

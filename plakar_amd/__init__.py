@@ -11,7 +11,9 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
     plakar_amd.encode      Repository.Encode on the device (DeviceEncoder)
     plakar_amd.decode      Repository.Decode and the blob check on the device (DeviceDecoder)
     plakar_amd.restore     packfiles and object records back to files (RestoreSession, restore_files)
+    plakar_amd.sync        blobs of one repository as blobs of another, on the device: re-key and
+                           re-encode (transcode_device), synchronize()'s loop over packfiles (SyncSession)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "sync", "build"]

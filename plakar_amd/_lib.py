@@ -105,6 +105,10 @@ class cdc_packfile_row(ctypes.Structure):
                 ("type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
 
 
+class cdc_codec(ctypes.Structure):
+    _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_char_p)]
+
+
 class cdc_restore_opts(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_void_p), ("verify", ctypes.c_int),
                 ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64)]
@@ -234,6 +238,11 @@ SIGNATURES = {
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                         ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32),
                                         ctypes.c_void_p]),
+    "cdc_transcode_size": (ctypes.c_int64, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int]),
+    "cdc_transcode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
+                                            ctypes.c_uint32, _P(cdc_codec), _P(cdc_codec), ctypes.c_char_p,
+                                            ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                            _P(ctypes.c_int32), ctypes.c_void_p]),
     "cdc_packfile_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, _P(cdc_packfile_footer),
                                           _P(cdc_packfile_row), ctypes.c_uint64, _P(ctypes.c_uint64)]),
     "cdc_assemble_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),

@@ -274,11 +274,13 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
-template <int N>
-__device__ __forceinline__ void aes256_blocks_lds(const GcmLds::PerWave &PW, const char *te, uint32_t laneoff,
+// (PW: anything with GcmLds::PerWave's rk and rk16; cdc_transcode.hip keeps a
+// second key set per wave that has no stage of its own.)
+template <int N, class PW>
+__device__ __forceinline__ void aes256_blocks_lds(const PW &pw, const char *te, uint32_t laneoff,
                                                   uint32_t (&st)[N][4])
 {
-    const uint32_t *rk = PW.rk, *rk16 = PW.rk16;
+    const uint32_t *rk = pw.rk, *rk16 = pw.rk16;
     auto A = [&](uint32_t w, uint32_t k) { return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k)); };
     auto B = [&](uint32_t w, uint32_t k) {
         return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k) + 128);
@@ -326,10 +328,10 @@ struct CtrPre {
     uint32_t r0, w1, v1, w2, w3, v3;  // round 2's constant terms
 };
 
-__device__ __forceinline__ CtrPre ctr_pre(const GcmLds::PerWave &PW, const char *te, uint32_t laneoff,
-                                          const uint32_t (&j0)[3])
+template <class PW>
+__device__ __forceinline__ CtrPre ctr_pre(const PW &pw, const char *te, uint32_t laneoff, const uint32_t (&j0)[3])
 {
-    const uint32_t *rk = PW.rk, *rk16 = PW.rk16;
+    const uint32_t *rk = pw.rk, *rk16 = pw.rk16;
     auto A = [&](uint32_t w, uint32_t k) { return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k)); };
     auto B = [&](uint32_t w, uint32_t k) {
         return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k) + 128);
@@ -353,11 +355,11 @@ __device__ __forceinline__ CtrPre ctr_pre(const GcmLds::PerWave &PW, const char 
 }
 
 // AES-256 of N counter blocks (J0[0..2], ctr[n]) of the piece CtrPre was made for.
-template <int N>
-__device__ __forceinline__ void aes256_ctr_lds(const GcmLds::PerWave &PW, const char *te, uint32_t laneoff,
-                                               const CtrPre &c, const uint32_t (&ctr)[N], uint32_t (&st)[N][4])
+template <int N, class PW>
+__device__ __forceinline__ void aes256_ctr_lds(const PW &pw, const char *te, uint32_t laneoff, const CtrPre &c,
+                                               const uint32_t (&ctr)[N], uint32_t (&st)[N][4])
 {
-    const uint32_t *rk = PW.rk, *rk16 = PW.rk16;
+    const uint32_t *rk = pw.rk, *rk16 = pw.rk16;
     auto A = [&](uint32_t w, uint32_t k) { return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k)); };
     auto B = [&](uint32_t w, uint32_t k) {
         return *reinterpret_cast<const uint32_t *>(te + te_addr(laneoff, w, k) + 128);
