@@ -184,6 +184,34 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
  * coded only when that is no larger than storing it). */
 uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
 
+/* ---- A gzip member written piece by piece ----------------------------------------
+ * The output pieces of one writer, concatenated, are one RFC 1952 member of
+ * the concatenated inputs, as gzip.NewWriter(out) ... Close() gives (the
+ * DEFLATE bytes are cdc_encode_device's kind, not Go's):
+ *   - the first piece starts with cdc_encode_device's ten header bytes;
+ *   - a piece is DEFLATE blocks with BFINAL clear, one per 32-KiB span, stored,
+ *     fixed or dynamic, whichever is smallest at the bit where it starts;
+ *   - an empty stored block (000, zeros to the byte boundary, 00 00 ff ff)
+ *     ends every piece on a byte boundary;
+ *   - the piece given with last != 0 then adds the final empty block
+ *     (01 00 00 ff ff), the CRC-32 of the whole stream and ISIZE, the
+ *     stream's length mod 2^32: a stream may be 4 GiB or longer.
+ * A stream with no bytes at all is still a whole member (header, final block,
+ * trailer).  len == 0 with last == 0 writes nothing.  A piece of 2 GiB or
+ * more is CDC_E_UNSUPPORTED.  d_in and d_out are device memory; the call is
+ * synchronous on `stream`, and calls on one writer are serialised.
+ * *out_len: the bytes written at d_out.  CDC_E_NOSPACE when out_cap is
+ * smaller, with *out_len the bytes needed, nothing written and the writer
+ * unchanged (the piece may be given again).  After the last piece every
+ * further piece is CDC_E_INVALID.  cdc_gzip_stream_bound(len): the most one
+ * call with len input bytes writes, header, joiner and trailer included. */
+typedef struct cdc_gzip_stream cdc_gzip_stream;
+int cdc_gzip_stream_new(int device, cdc_gzip_stream **out);
+uint64_t cdc_gzip_stream_bound(uint64_t len);
+int cdc_gzip_stream_piece(cdc_gzip_stream *s, const void *d_in, uint64_t len, int last, uint8_t *d_out,
+                          uint64_t out_cap, uint64_t *out_len, void *stream);
+void cdc_gzip_stream_free(cdc_gzip_stream *s);
+
 /* ---- Decode: open the AES-256-GCM stream, then inflate (LZ4 or GZIP) -------------
  * (*Repository).Decode (repository/repository.go:186-210) of n encoded blobs
  * that sit in device memory at d_in + offsets[i], lens[i] bytes each:
@@ -600,6 +628,77 @@ int cdc_restore_add_packfile_path(cdc_restore *r, const char *path);
 int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
                       cdc_restore_stats *stats);
 void cdc_restore_free(cdc_restore *r);
+
+/* ---- archive: a snapshot's entries as one tar or tar.gz stream -------------------
+ * `plakar archive` (cmd/plakar/subcommands/archive/archive.go) for its tar and
+ * tarball formats.  The caller supplies the entries (it walks the snapshot, as
+ * it supplies objects to restore): files with their chunk lists, and
+ * directories.  The tar stream is entries in caller order: a POSIX ustar
+ * header block (magic "ustar\0", version "00", uid/gid 0, no uname/gname,
+ * typeflag 0 or 5, mtime in whole seconds; a name over 100 bytes split at a
+ * "/" into prefix and name), the file's bytes, zeros to the next 512; 1,024
+ * zeros at the end and no blocking-factor padding (archive/tar's Close).  An
+ * entry that does not fit the block gets a PAX extended header first with the
+ * records archive/tar would choose: path (no valid split, over 255 bytes, or a
+ * byte >= 0x80), size (8 GiB or more), mtime (negative or over eleven octal
+ * digits).  `mode` is the permission bits, 0..07777 (the reference passes Go's
+ * FileMode with its type bits; that is not reproduced).
+ * CDC_ARCHIVE_TARGZ puts the stream through one cdc_gzip_stream: one member.
+ *   compress, key, verify, writers, batch_bytes: as cdc_restore_opts, the
+ *     batch counted in bytes of tar stream (0: 256 MiB; at most 1 GiB).
+ * Output goes to `path` (created, truncated) or, with path == NULL, to
+ * on_data in stream order (a nonzero return ends the run with CDC_E_IO).
+ * Failures: an entry with a checksum in no registered packfile is left out
+ * whole, header included; on_entry gets CDC_E_NOTFOUND for it and the run goes
+ * on.  A blob that cannot be read or fails Decode, whose decoded length is not
+ * its recorded Length or whose SHA-256 differs ends the run with that status;
+ * on_entry and stats->failed_entry name the first entry that uses it, nothing
+ * more is written and a `path` output is removed.  After a run that succeeds
+ * on_entry gets CDC_OK for every entry in the archive.  on_entry may be NULL.
+ * stats (may be NULL): the caller sets struct_size; at most that many bytes
+ * are written. */
+#define CDC_ARCHIVE_TAR   0
+#define CDC_ARCHIVE_TARGZ 1
+#define CDC_ARCHIVE_FILE  0
+#define CDC_ARCHIVE_DIR   1
+typedef struct cdc_archive_opts {
+    uint32_t struct_size;  /* sizeof(cdc_archive_opts) */
+    int compress;          /* the repository's: CDC_COMPRESS_NONE, _LZ4 or _GZIP */
+    const uint8_t *key;    /* 32-byte repository key, or NULL */
+    int verify;
+    int writers;           /* reader threads (0: 8) */
+    uint64_t batch_bytes;
+    int format;            /* CDC_ARCHIVE_TAR or CDC_ARCHIVE_TARGZ */
+} cdc_archive_opts;
+/* struct_size set, verify = 1, format = CDC_ARCHIVE_TARGZ (the reference's default), everything else 0. */
+void cdc_archive_default_opts(cdc_archive_opts *out);
+typedef struct cdc_archive_entry {
+    const char *name;
+    int type;                  /* CDC_ARCHIVE_FILE or CDC_ARCHIVE_DIR */
+    uint32_t mode;
+    int64_t mtime;
+    uint64_t nchunks;          /* files: Object.Chunks */
+    const uint8_t *checksums;  /* 32 B per chunk */
+    const uint32_t *lengths;
+} cdc_archive_entry;
+typedef struct cdc_archive_stats {
+    uint32_t struct_size;
+    int32_t failed_entry;      /* the entry a failed run names, or -1 */
+    uint64_t entries, skipped_entries;   /* in the archive; left out (CDC_E_NOTFOUND) */
+    uint64_t stream_bytes, output_bytes; /* tar stream; what was written (tar.gz: compressed) */
+    uint64_t segments, decoded_blobs, encoded_bytes, decoded_bytes, batches;
+    double read_s, h2d_s, decode_s, verify_s, assemble_s, deflate_s, d2h_s, write_s;  /* each stage, summed */
+    double wall_s;
+} cdc_archive_stats;
+typedef int (*cdc_archive_data_fn)(void *ctx, const uint8_t *data, uint64_t len);
+typedef void (*cdc_archive_entry_fn)(void *ctx, int index, int status);
+typedef struct cdc_archive cdc_archive;
+int cdc_archive_new(int device, const cdc_archive_opts *opts, cdc_archive **out);
+int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
+int cdc_archive_add_packfile_path(cdc_archive *a, const char *path);
+int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path,
+                    cdc_archive_data_fn on_data, cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats);
+void cdc_archive_free(cdc_archive *a);
 
 /* The library's host SHA-256 (x86 SHA extensions when the CPU has them;
  * force_scalar != 0 takes the portable path).  cdc_sha256_accelerated: 1 if

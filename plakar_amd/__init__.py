@@ -13,7 +13,9 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
     plakar_amd.restore     packfiles and object records back to files (RestoreSession, restore_files)
     plakar_amd.sync        blobs of one repository as blobs of another, on the device: re-key and
                            re-encode (transcode_device), synchronize()'s loop over packfiles (SyncSession)
+    plakar_amd.archive     a snapshot's entries as one tar or tar.gz stream (ArchiveSession, archive_files);
+                           a gzip member written piece by piece on the device (GzipStream)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "sync", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "sync", "archive", "build"]

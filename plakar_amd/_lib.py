@@ -133,6 +133,30 @@ class cdc_restore_stats(ctypes.Structure):
                                                "write_s", "wall_s")]
 
 
+class cdc_archive_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
+                ("verify", ctypes.c_int), ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
+                ("format", ctypes.c_int)]
+
+
+class cdc_archive_entry(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char_p), ("type", ctypes.c_int), ("mode", ctypes.c_uint32),
+                ("mtime", ctypes.c_int64), ("nchunks", ctypes.c_uint64), ("checksums", ctypes.c_void_p),
+                ("lengths", ctypes.c_void_p)]
+
+
+class cdc_archive_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("failed_entry", ctypes.c_int32)] + \
+               [(n, ctypes.c_uint64) for n in ("entries", "skipped_entries", "stream_bytes", "output_bytes", "segments",
+                                               "decoded_blobs", "encoded_bytes", "decoded_bytes", "batches")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "assemble_s", "deflate_s",
+                                               "d2h_s", "write_s", "wall_s")]
+
+
+CDC_ARCHIVE_TAR, CDC_ARCHIVE_TARGZ = 0, 1
+CDC_ARCHIVE_FILE, CDC_ARCHIVE_DIR = 0, 1
+ARCHIVE_DATA_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
+ARCHIVE_ENTRY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)
 RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_restore_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
@@ -231,6 +255,11 @@ SIGNATURES = {
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                          ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
     "cdc_encode_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int]),
+    "cdc_gzip_stream_new": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_void_p)]),
+    "cdc_gzip_stream_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "cdc_gzip_stream_piece": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
+    "cdc_gzip_stream_free": (None, [ctypes.c_void_p]),
     "cdc_decode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
                                          ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_void_p]),
@@ -256,6 +285,13 @@ SIGNATURES = {
     "cdc_restore_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, RESTORE_FILE_FN,
                                          ctypes.c_void_p, _P(cdc_restore_stats)]),
     "cdc_restore_free": (None, [ctypes.c_void_p]),
+    "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
+    "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
+    "cdc_archive_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_archive_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_archive_run": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_archive_entry), ctypes.c_int, ctypes.c_char_p,
+                                       ARCHIVE_DATA_FN, ARCHIVE_ENTRY_FN, ctypes.c_void_p, _P(cdc_archive_stats)]),
+    "cdc_archive_free": (None, [ctypes.c_void_p]),
     "cdc_set_debug_mode": (ctypes.c_int, [ctypes.c_int]),
     "cdc_gear_is_placeholder": (ctypes.c_int, []),
     "cdc_set_maskl_index_mode": (ctypes.c_int, [ctypes.c_int]),

@@ -1,0 +1,426 @@
+// cdc_archive_*: a snapshot's entries as one tar or tar.gz stream
+// (include/plakar_cdc.h, "archive").
+//
+// The reference (cmd/plakar/subcommands/archive/archive.go:125-190) reads each
+// file chunk by chunk (one GetBlob and one Decode per chunk, a chunk that
+// occurs twice decoded twice), copies the bytes into an archive/tar writer and,
+// for its default format, pushes the whole tar stream through one
+// gzip.NewWriter.  Here the tar stream is planned up front (archive_plan.h) in
+// batches of stream bytes, and a batch goes through
+//
+//   read      its distinct encoded blobs, gathered into a pinned arena
+//             (memcpy or pread, on `writers` threads) with the batch's header
+//             blocks and a zero block behind them;
+//   H2D       one copy of each;
+//   Decode    (+ verify) over the distinct blobs, as restore's;
+//   assemble  cdc_assemble_device: chunk occurrences, header blocks and
+//             padding into the batch's image of the tar stream;
+//   deflate   tar.gz: cdc_gzip_stream_piece over the image, one member for
+//             the whole run;
+//   D2H       the image, or for tar.gz only the compressed bytes;
+//   write     to the path or to on_data, in stream order.
+//
+// The stages of one batch run one after the other on the calling thread and
+// batches do not overlap yet (restore's three-thread rotation is the model for
+// that step); every stage's seconds are in the stats.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "archive_plan.h"
+#include "cdc_hostmem.h"
+#include "cdc_internal.h"
+#include "cdc_locator.h"
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+template <class F>
+static void parallel_for(int threads, size_t n, F fn)
+{
+    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
+    if (t <= 1) {
+        for (size_t i = 0; i < n; ++i) fn(i);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+}
+
+constexpr uint64_t kMaxBatch = 1ull << 30;  // a batch's image is one gzip piece: under 2 GiB with its largest chunk
+
+}  // namespace
+
+struct cdc_archive {
+    int device = 0;
+    cdc_archive_opts o{};
+    std::vector<uint8_t> key;
+    cdc::Locator loc;
+    hipStream_t stream = nullptr;
+    cdc::PinBuf h_in, h_out;
+    cdc::DevBuf d_in, d_plain, d_img, d_gz;
+    std::mutex run_mu;
+};
+
+namespace {
+
+struct Run {
+    cdc_archive *A;
+    cdc_archive_data_fn on_data;
+    void *ctx;
+    int fd = -1;
+    std::vector<int> pidx;  // planned entry -> index in entries
+    cdc_archive_stats st{};
+    int failed = -1;        // the entry a failure names
+
+    int emit(const uint8_t *p, uint64_t len)
+    {
+        if (!len) return CDC_OK;
+        st.output_bytes += len;
+        if (fd >= 0) return cdc::write_all(fd, p, len) ? CDC_OK : CDC_E_IO;
+        return on_data && on_data(ctx, p, len) == 0 ? CDC_OK : CDC_E_IO;
+    }
+};
+
+// One batch through every stage; CDC_OK or the run's failure (X.failed set when a blob is to blame).
+static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool last)
+{
+    cdc_archive *A = X.A;
+    const cdc::Locator &L = A->loc;
+    const uint32_t nb = uint32_t(B.blobs.size());
+    hipStream_t s = A->stream;
+    // read
+    auto t0 = Clock::now();
+    std::vector<uint64_t> eoff(nb), elen(nb);
+    std::vector<int32_t> pre(nb, CDC_OK);
+    uint64_t enc = 0;
+    std::unordered_map<uint32_t, int> fds;
+    for (uint32_t b = 0; b < nb; ++b) {
+        const cdc::Locator::Loc &l = L.locs[B.blobs[b].id];
+        eoff[b] = enc;
+        elen[b] = l.length;
+        enc += l.length;
+        const cdc::Locator::Pack &P = L.packs[l.pack];
+        if (!P.mem && !fds.count(l.pack)) fds[l.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
+    }
+    const uint64_t h_arena = cdc::align_up(enc, 16), arena_base = cdc::align_up(B.plain_bytes, 16);
+    const uint64_t plain_cap = arena_base + B.arena.size();
+    auto close_fds = [&] {
+        for (auto &f : fds)
+            if (f.second >= 0) close(f.second);
+    };
+    if (!A->h_in.reserve(h_arena + B.arena.size()) || !A->d_in.reserve(enc) || !A->d_plain.reserve(plain_cap) ||
+        !A->d_img.reserve(B.out_bytes)) {
+        close_fds();
+        return CDC_E_NOMEM;
+    }
+    uint8_t *const h = A->h_in.as<uint8_t>();
+    parallel_for(A->o.writers, nb, [&](size_t b) {
+        const cdc::Locator::Loc &l = L.locs[B.blobs[b].id];
+        const cdc::Locator::Pack &P = L.packs[l.pack];
+        if (P.mem) {
+            std::memcpy(h + eoff[b], P.mem + l.offset, l.length);
+            return;
+        }
+        const int fd = fds.find(l.pack)->second;
+        if (fd < 0 || !cdc::pread_all(fd, h + eoff[b], l.length, l.offset)) pre[b] = CDC_E_IO;
+    });
+    close_fds();
+    std::memcpy(h + h_arena, B.arena.data(), B.arena.size());
+    X.st.read_s += since(t0);
+    X.st.encoded_bytes += enc;
+    // which entry a blob belongs to (its first use in the batch), for a failure's name
+    auto blame = [&](uint32_t b, int status) {
+        for (const aplan::Segment &S : B.segs)
+            if (!S.arena && S.blob == b) {
+                X.failed = X.pidx[S.entry];
+                break;
+            }
+        return status;
+    };
+    for (uint32_t b = 0; b < nb; ++b)
+        if (pre[b] != CDC_OK) return blame(b, pre[b]);
+    // H2D
+    t0 = Clock::now();
+    uint8_t *const plain = A->d_plain.as<uint8_t>();
+    if ((enc && hipMemcpyAsync(A->d_in.data(), h, enc, hipMemcpyHostToDevice, s) != hipSuccess) ||
+        hipMemcpyAsync(plain + arena_base, h + h_arena, B.arena.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return CDC_E_DEVICE;
+    X.st.h2d_s += since(t0);
+    // Decode (+ verify)
+    std::vector<uint64_t> oo(size_t(nb) + 1, 0);
+    std::vector<int32_t> bst(std::max<uint32_t>(nb, 1), CDC_OK);
+    std::vector<uint8_t> want;
+    if (A->o.verify) {
+        want.resize(size_t(nb) * 32 + 1);
+        for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], L.sums[B.blobs[b].id].b, 32);
+    }
+    const uint8_t *key = A->key.empty() ? nullptr : A->key.data();
+    const uint8_t *sums = A->o.verify ? want.data() : nullptr;
+    if (nb) {
+        int st = cdc::decode_checked(A->device, A->d_in.data(), eoff.data(), elen.data(), nb, A->o.compress, key, sums, plain,
+                                     B.plain_bytes, oo.data(), bst.data(), s, &X.st.decode_s, &X.st.verify_s);
+        if (st == CDC_E_NOSPACE) {
+            // some blob decodes to more than its recorded Length: one by one, each
+            // into the room its Length gives it, to name it
+            for (uint32_t b = 0; b < nb; ++b) {
+                uint64_t o2[2] = {0, 0};
+                int32_t one = CDC_OK;
+                st = cdc::decode_checked(A->device, A->d_in.data(), &eoff[b], &elen[b], 1, A->o.compress, key,
+                                         sums ? sums + size_t(b) * 32 : nullptr, plain, B.blobs[b].len, o2, &one, s,
+                                         &X.st.decode_s, &X.st.verify_s);
+                if (st == CDC_E_NOSPACE) return blame(b, CDC_E_MISMATCH);
+                if (st != CDC_OK) return st;
+                if (one != CDC_OK) return blame(b, one);
+            }
+            return CDC_E_MISMATCH;
+        }
+        if (st != CDC_OK) return st;
+        for (uint32_t b = 0; b < nb; ++b) {
+            if (bst[b] != CDC_OK) return blame(b, bst[b]);
+            if (oo[b + 1] - oo[b] != B.blobs[b].len) return blame(b, CDC_E_MISMATCH);
+        }
+        X.st.decoded_bytes += oo[nb];
+    }
+    // assemble
+    t0 = Clock::now();
+    {
+        const size_t ns = B.segs.size();
+        std::vector<uint64_t> so(ns), sl(ns), sd(ns);
+        for (size_t i = 0; i < ns; ++i) {
+            const aplan::Segment &S = B.segs[i];
+            so[i] = S.arena ? arena_base + S.src_off : oo[S.blob];
+            sl[i] = S.len;
+            sd[i] = S.dst_off;
+        }
+        const int st = cdc_assemble_device(A->device, plain, plain_cap, so.data(), sl.data(), sd.data(), ns, A->d_img.data(),
+                                           B.out_bytes, s);
+        if (st != CDC_OK) return st;
+        if (hipStreamSynchronize(s) != hipSuccess) return CDC_E_DEVICE;
+    }
+    X.st.assemble_s += since(t0);
+    // deflate
+    const uint8_t *d_src = A->d_img.as<uint8_t>();
+    uint64_t out_len = B.out_bytes;
+    if (gz) {
+        t0 = Clock::now();
+        const uint64_t cap = cdc_gzip_stream_bound(B.out_bytes);
+        if (!A->d_gz.reserve(cap)) return CDC_E_NOMEM;
+        const int st = cdc_gzip_stream_piece(gz, d_src, B.out_bytes, last ? 1 : 0, A->d_gz.as<uint8_t>(), cap, &out_len, s);
+        if (st != CDC_OK) return st;
+        d_src = A->d_gz.as<uint8_t>();
+        X.st.deflate_s += since(t0);
+    }
+    // D2H
+    t0 = Clock::now();
+    if (!A->h_out.reserve(out_len)) return CDC_E_NOMEM;
+    if (out_len && (hipMemcpyAsync(A->h_out.data(), d_src, out_len, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess))
+        return CDC_E_DEVICE;
+    X.st.d2h_s += since(t0);
+    // write
+    t0 = Clock::now();
+    const int st = X.emit(A->h_out.as<uint8_t>(), out_len);
+    X.st.write_s += since(t0);
+    return st;
+}
+
+static int run(cdc_archive *A, const cdc_archive_entry *entries, int n, const char *path, cdc_archive_data_fn on_data,
+               cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats)
+{
+    const auto w0 = Clock::now();
+    Run X{};
+    X.A = A;
+    X.on_data = on_data;
+    X.ctx = ctx;
+    auto finish = [&](int st) {
+        X.st.failed_entry = st == CDC_OK ? -1 : X.failed;
+        X.st.wall_s = since(w0);
+        if (stats) {
+            X.st.struct_size = uint32_t(std::min<size_t>(stats->struct_size, sizeof(X.st)));
+            std::memcpy(stats, &X.st, X.st.struct_size);
+        }
+        return st;
+    };
+    // the locator: every chunk's blob id; an entry with a checksum in no
+    // packfile is left out whole, header included, and the run goes on
+    std::vector<std::vector<uint32_t>> fblob;
+    std::vector<std::vector<uint8_t>> hdrs;
+    for (int i = 0; i < n; ++i) {
+        const cdc_archive_entry &E = entries[i];
+        const bool dir = E.type == CDC_ARCHIVE_DIR;
+        std::vector<uint32_t> ids(dir ? 0 : size_t(E.nchunks));
+        uint64_t size = 0;
+        bool found = true;
+        for (uint64_t c = 0; c < ids.size() && found; ++c) {
+            cdc::Sum s;
+            std::memcpy(s.b, E.checksums + 32 * c, 32);
+            const auto it = A->loc.index.find(s);
+            found = it != A->loc.index.end();
+            if (found) ids[size_t(c)] = it->second;
+            size += E.lengths[c];
+        }
+        if (!found) {
+            ++X.st.skipped_entries;
+            if (on_entry) on_entry(ctx, i, CDC_E_NOTFOUND);
+            continue;
+        }
+        std::vector<uint8_t> h;
+        const aplan::Entry pe{E.name, std::strlen(E.name), E.type, E.mode, E.mtime, size};
+        const int st = aplan::build_header(pe, h);
+        if (st != CDC_OK) {  // a name or mode no header can carry: nothing is written
+            X.failed = i;
+            if (on_entry) on_entry(ctx, i, st);
+            return finish(st);
+        }
+        fblob.push_back(std::move(ids));
+        hdrs.push_back(std::move(h));
+        X.pidx.push_back(i);
+    }
+    std::vector<aplan::File> pf;
+    for (size_t p = 0; p < X.pidx.size(); ++p)
+        pf.push_back(aplan::File{hdrs[p].data(), hdrs[p].size(), fblob[p].size(), fblob[p].data(), entries[X.pidx[p]].lengths});
+    std::vector<aplan::Batch> batches;
+    aplan::plan(pf.data(), pf.size(), A->o.batch_bytes, batches);
+    for (const aplan::Batch &B : batches) {
+        X.st.stream_bytes += B.out_bytes;
+        X.st.segments += B.segs.size();
+        X.st.decoded_blobs += B.blobs.size();
+    }
+    X.st.batches = batches.size();
+    X.st.entries = X.pidx.size();
+    if (hipSetDevice(A->device) != hipSuccess) return finish(CDC_E_DEVICE);
+    if (path) {
+        X.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+        if (X.fd < 0) return finish(CDC_E_IO);
+    }
+    cdc_gzip_stream *gz = nullptr;
+    int st = A->o.format == CDC_ARCHIVE_TARGZ ? cdc_gzip_stream_new(A->device, &gz) : CDC_OK;
+    for (size_t k = 0; k < batches.size() && st == CDC_OK; ++k) st = run_batch(X, batches[k], gz, k + 1 == batches.size());
+    cdc_gzip_stream_free(gz);
+    if (X.fd >= 0) {
+        if (close(X.fd) != 0 && st == CDC_OK) st = CDC_E_IO;
+        if (st != CDC_OK) unlink(path);  // nothing is left behind: the reference's log.Fatal before its rename
+    }
+    if (on_entry) {
+        if (st == CDC_OK)
+            for (int i : X.pidx) on_entry(ctx, i, CDC_OK);
+        else if (X.failed >= 0)
+            on_entry(ctx, X.failed, st);
+    }
+    return finish(st);
+}
+
+}  // namespace
+
+extern "C" {
+
+void cdc_archive_default_opts(cdc_archive_opts *out)
+{
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->verify = 1;
+    out->format = CDC_ARCHIVE_TARGZ;  // the reference's default, "tarball"
+}
+
+int cdc_archive_new(int device, const cdc_archive_opts *opts, cdc_archive **out)
+{
+    if (!opts || !out) return CDC_E_INVALID;
+    *out = nullptr;
+    if (opts->struct_size != sizeof(*opts) || device < 0 || device >= cdc::kMaxDevices || opts->writers < 0 ||
+        opts->writers > 256 || (opts->format != CDC_ARCHIVE_TAR && opts->format != CDC_ARCHIVE_TARGZ))
+        return CDC_E_INVALID;
+    if (!cdc::device_count_initialised()) return CDC_E_NOT_INIT;
+    auto *a = new (std::nothrow) cdc_archive();
+    if (!a) return CDC_E_NOMEM;
+    try {
+        a->device = device;
+        a->o = *opts;
+        if (opts->key) a->key.assign(opts->key, opts->key + 32);
+        a->o.key = nullptr;
+        if (!a->o.writers) a->o.writers = 8;
+        if (!a->o.batch_bytes) a->o.batch_bytes = 256ull << 20;
+        a->o.batch_bytes = std::min<uint64_t>(a->o.batch_bytes, kMaxBatch);
+    } catch (...) {
+        delete a;
+        return CDC_E_NOMEM;
+    }
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
+        cdc_archive_free(a);
+        return CDC_E_DEVICE;
+    }
+    *out = a;
+    return CDC_OK;
+}
+
+int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len)
+{
+    if (!a || (!bytes && len)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(a->run_mu);
+    try {
+        return a->loc.add_memory(bytes, len);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_archive_add_packfile_path(cdc_archive *a, const char *path)
+{
+    if (!a || !path) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(a->run_mu);
+    try {
+        return a->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path, cdc_archive_data_fn on_data,
+                    cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats)
+{
+    if (!a || n < 0 || (n && !entries) || (!path && !on_data)) return CDC_E_INVALID;
+    if (stats && stats->struct_size < 8) return CDC_E_INVALID;
+    for (int i = 0; i < n; ++i) {
+        const cdc_archive_entry &E = entries[i];
+        if (!E.name || (E.type != CDC_ARCHIVE_FILE && E.type != CDC_ARCHIVE_DIR)) return CDC_E_INVALID;
+        if (E.type == CDC_ARCHIVE_FILE && E.nchunks && (!E.checksums || !E.lengths)) return CDC_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(a->run_mu);
+    try {
+        return run(a, entries, n, path, on_data, on_entry, ctx, stats);
+    } catch (const std::bad_alloc &) {
+        return CDC_E_NOMEM;
+    }
+}
+
+void cdc_archive_free(cdc_archive *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    if (a->stream) {
+        (void)hipStreamSynchronize(a->stream);
+        (void)hipStreamDestroy(a->stream);
+    }
+    if (!a->key.empty()) std::memset(a->key.data(), 0, a->key.size());
+    delete a;
+}
+
+}  // extern "C"

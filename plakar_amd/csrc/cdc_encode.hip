@@ -50,11 +50,20 @@
 //   k_gz_fin      one wave per blob: header, the bytes two spans share, the
 //                 CRC-32 combined from the spans', ISIZE
 // in the place of k_xxh32, k_lz4_size, k_lz4_emit and k_frame_fin.
+//
+// cdc_gzip_stream_piece writes one gzip member piece by piece (archive's
+// tarball): a piece is one blob of such a batch with no final block, and
+//   k_gzs_plan    one wave: each span's form at its bit, the joiner, the
+//                 piece's length against out_cap
+//   k_gzs_fin     one wave: header (first piece), shared bytes, the joiner,
+//                 the piece's CRC-32; final block and trailer (last piece)
+// stand in the place of k_enc_plan and k_gz_fin.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "cdc_internal.h"
@@ -1338,6 +1347,101 @@ __global__ __launch_bounds__(64) void k_gz_fin(const Batch B)
 }
 
 // ---------------------------------------------------------------------------
+// The stream form (cdc_gzip_stream_piece): one member out of many pieces.  A
+// piece is planned as one blob of a GZIP batch (k_lz4_seq, k_dfl_size and
+// k_dfl_emit run unchanged, no span marked last), with these two kernels in
+// the place of k_enc_plan and k_gz_fin.  They stand behind the GCM kernels
+// like the other DEFLATE kernels.
+// ---------------------------------------------------------------------------
+struct StreamArgs {
+    uint32_t first, last;  // the member's first piece (header), its last (final block, CRC-32, ISIZE)
+    uint32_t reg;          // CRC-32 register over the stream before this piece, from 0xFFFFFFFF
+    uint32_t isize;        // the stream's length with this piece, mod 2^32
+    uint64_t *res;         // [0]: the piece's output bytes; [1]: its CRC-32 register from 0
+};
+
+// One wave: each span's form at the bit where the block before it ended.  The
+// lanes load 64 spans' sizes at a time; the chain over them runs in registers,
+// alike in every lane, and lane j keeps span j's result.
+__global__ __launch_bounds__(64) void k_gzs_plan(const Batch B, const StreamArgs A)
+{
+    const uint32_t lane = threadIdx.x;
+    uint64_t P = A.first ? 80 : 0;
+    for (uint32_t s0 = 0; s0 < B.nspans; s0 += 64) {
+        const uint32_t sp = s0 + lane;
+        const bool in = sp < B.nspans;
+        const uint32_t len = in ? B.spans[sp].len : 0u;
+        const uint32_t fb = in ? B.sp[sp].fixed_bits : 0u, db = in ? B.sp[sp].dyn_bits : 0u;
+        uint32_t ty = 0, nb = 0;
+        uint64_t at = 0;
+        const uint32_t cnt = min(64u, B.nspans - s0);
+        for (uint32_t j = 0; j < cnt; ++j) {
+            uint64_t bits;
+            const uint32_t t = dfl::choose_block(P, uint32_t(__shfl(int(len), int(j))), uint32_t(__shfl(int(fb), int(j))),
+                                                 uint32_t(__shfl(int(db), int(j))), bits);
+            if (lane == j) {
+                ty = t;
+                nb = uint32_t(bits);
+                at = P;
+            }
+            P += bits;
+        }
+        if (in) {
+            SpanOut &o = B.sp[sp];
+            o.type = ty;
+            o.nbits = nb;
+            o.bit = at;
+        }
+    }
+    if (lane == 0) {
+        P += dfl::joiner_bits(P);
+        const uint64_t F = P / 8 + (A.last ? dfl::kFinalBytes + 8 : 0);
+        B.frame_len[0] = F;
+        B.out_off[0] = 0;
+        B.out_off[1] = F;
+        B.status[0] = F > B.out_cap ? uint64_t(uint32_t(CDC_E_NOSPACE)) : 0ull;
+        B.status[1] = 0;
+        A.res[0] = F;
+        A.res[1] = 0;
+    }
+}
+
+// One wave: the header (first piece), the bytes two spans' blocks share, the
+// joiner, the piece's CRC-32 register for the host's running one and, on the
+// last piece, the final block, the stream's CRC-32 and ISIZE.
+__global__ __launch_bounds__(64) void k_gzs_fin(const Batch B, const StreamArgs A)
+{
+    const uint32_t lane = threadIdx.x;
+    if (B.status[0]) return;
+    uint8_t *f = B.out;
+    const uint64_t len = B.blobs[0].len;
+    const uint32_t n = B.nspans;  // >= 1: an empty piece never comes here
+    if (A.first && lane < 10) f[lane] = lane == 0 ? 0x1F : lane == 1 ? 0x8B : lane == 2 ? 8 : lane == 9 ? 0xFF : 0;
+    uint32_t acc = 0;
+    for (uint32_t k = lane; k < n; k += 64) {
+        const SpanOut &o = B.sp[k];
+        const uint64_t done = min<uint64_t>(len, uint64_t(k + 1) * dfl::kSpan);
+        acc ^= infw::crc_mul(o.crc, infw::crc_shift(len - done));
+        if (k && (o.bit & 7u)) f[o.bit >> 3] = uint8_t(B.sp[k - 1].edge_hi | o.edge_lo);
+    }
+    for (int o = 32; o; o >>= 1) acc ^= __shfl_xor(acc, o);
+    if (lane == 0) {
+        const SpanOut &o = B.sp[n - 1];
+        const uint64_t E = o.bit + o.nbits;
+        uint8_t *e = f + (E >> 3);
+        e += dfl::stream_end(e, o.edge_hi, uint32_t(E & 7u), A.last != 0);
+        if (A.last) {
+            const uint32_t crc = ~(acc ^ infw::crc_mul(A.reg, infw::crc_shift(len)));
+            for (int i = 0; i < 4; ++i) {
+                e[i] = uint8_t(crc >> (8 * i));
+                e[4 + i] = uint8_t(A.isize >> (8 * i));
+            }
+        }
+        A.res[1] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 static cdc::AesTables g_tab;
@@ -1590,4 +1694,179 @@ extern "C" uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt)
 {
     const uint64_t f = frame_max(len, (len + kBlockLZ - 1) / kBlockLZ, compress);
     return encrypt ? 60 + f + 28 * ((f + kPiece - 1) / kPiece) : f;
+}
+
+// ---------------------------------------------------------------------------
+// The streamed gzip member (see include/plakar_cdc.h).  The writer owns its
+// workspace, so it shares nothing with cdc_encode_device's; the running CRC-32
+// register and length live here, on the host.
+// ---------------------------------------------------------------------------
+struct cdc_gzip_stream {
+    int device = 0;
+    bool first = true, closed = false;
+    uint32_t reg = 0xFFFFFFFFu;  // CRC-32 register over the bytes so far
+    uint64_t total = 0;
+    std::mutex mu;
+    cdc::DevBuf ws;
+    cdc::PinBuf stage;
+};
+
+extern "C" int cdc_gzip_stream_new(int device, cdc_gzip_stream **out)
+{
+    if (!out || device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;
+    cdc_gzip_stream *s = new (std::nothrow) cdc_gzip_stream;
+    if (!s) return CDC_E_NOMEM;
+    s->device = device;
+    *out = s;
+    return CDC_OK;
+}
+
+extern "C" void cdc_gzip_stream_free(cdc_gzip_stream *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
+}
+
+extern "C" uint64_t cdc_gzip_stream_bound(uint64_t len) { return dfl::stream_piece_bound(len); }
+
+extern "C" int cdc_gzip_stream_piece(cdc_gzip_stream *S, const void *d_in, uint64_t len, int last, uint8_t *d_out,
+                                     uint64_t out_cap, uint64_t *out_len, void *stream)
+{
+    if (!S || !out_len || (len && !d_in)) return CDC_E_INVALID;
+    *out_len = 0;
+    if (len > dfl::kMaxBlob) return CDC_E_UNSUPPORTED;  // a piece's bit positions and spans are planned like a blob's
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (S->closed) return CDC_E_INVALID;
+    if (len == 0 && !last) return CDC_OK;
+    if (!d_out) return CDC_E_INVALID;
+    if (hipSetDevice(S->device) != hipSuccess) return CDC_E_DEVICE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (len == 0) {
+        // nothing to deflate: the header when no piece came before, the final
+        // block and the trailer, written here (gzip.Writer's Close: a stream
+        // with no bytes at all is still a whole member)
+        uint8_t b[10 + dfl::kFinalBytes + 8];
+        uint32_t n = 0;
+        if (S->first) {
+            const uint8_t hdr[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF};
+            std::memcpy(b, hdr, 10);
+            n = 10;
+        }
+        const uint8_t fin[dfl::kFinalBytes] = {1, 0, 0, 0xFF, 0xFF};
+        std::memcpy(b + n, fin, sizeof(fin));
+        n += dfl::kFinalBytes;
+        const uint32_t crc = ~S->reg;
+        for (int i = 0; i < 4; ++i) {
+            b[n + i] = uint8_t(crc >> (8 * i));
+            b[n + 4 + i] = uint8_t(uint32_t(S->total) >> (8 * i));
+        }
+        n += 8;
+        *out_len = n;
+        if (n > out_cap) return CDC_E_NOSPACE;
+        if (hipMemcpyAsync(d_out, b, n, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return CDC_E_DEVICE;
+        S->first = false;
+        S->closed = true;
+        return CDC_OK;
+    }
+    // the piece as one blob of a GZIP batch: 4-MiB blocks (the match search's
+    // end-of-block rules), 8-KiB segments, 32-KiB spans
+    const size_t nk = size_t((len + kBlockLZ - 1) / kBlockLZ), ng = size_t((len + kSegLZ - 1) / kSegLZ),
+                 nsp = size_t((len + dfl::kSpan - 1) / dfl::kSpan);
+    cdc::Carver cv(16);
+    const size_t o_blobs = cv.take(sizeof(BlobDesc)), o_segs = cv.take(ng * sizeof(Seg)),
+                 o_spans = cv.take(nsp * sizeof(Span)), o_bsp = cv.take(2 * 4);
+    const size_t h_prefix = cv.bytes();
+    const size_t o_recs = cv.take(ng * kRecCap * sizeof(uint2)), o_nrec = cv.take(ng * 4), o_trail = cv.take(ng * 4);
+    const size_t o_flen = cv.take(8), o_oo = cv.take(2 * 8), o_status = cv.take(16), o_res = cv.take(16);
+    const size_t o_sp = cv.take(nsp * sizeof(SpanOut)), o_splens = cv.take(nsp * kSpanLens),
+                 o_sphdr = cv.take(nsp * dfl::kHdrWords * 4);
+    if (!S->ws.reserve(cv.bytes())) return CDC_E_DEVICE;
+    if (!S->stage.reserve(h_prefix)) return CDC_E_NOMEM;
+    uint8_t *const ws = S->ws.as<uint8_t>(), *const hp = S->stage.as<uint8_t>();
+    {
+        BlobDesc D{};
+        D.len = len;
+        D.nblk = uint32_t(nk);
+        std::memcpy(hp + o_blobs, &D, sizeof(D));
+        Seg *segs = reinterpret_cast<Seg *>(hp + o_segs);
+        Span *spans = reinterpret_cast<Span *>(hp + o_spans);
+        uint32_t *bsp = reinterpret_cast<uint32_t *>(hp + o_bsp);
+        size_t kg = 0, ks = 0;
+        for (size_t k = 0; k < nk; ++k) {
+            const uint64_t src = k * kBlockLZ;
+            const uint32_t blen = uint32_t(std::min<uint64_t>(kBlockLZ, len - src));
+            const uint32_t nseg = (blen + kSegLZ - 1) / kSegLZ;
+            for (uint32_t g = 0; g < nseg; g += dfl::kSpanSegs) {
+                Span P{};
+                P.src = src + uint64_t(g) * kSegLZ;
+                P.len = std::min<uint32_t>(dfl::kSpan, blen - g * kSegLZ);
+                P.seg0 = uint32_t(kg + g);
+                P.nseg = std::min<uint32_t>(dfl::kSpanSegs, nseg - g);
+                P.k = uint32_t(ks);
+                spans[ks++] = P;  // last = 0: no block of a piece carries BFINAL
+            }
+            for (uint32_t g = 0; g < nseg; ++g) {
+                Seg G{};
+                G.src = src + uint64_t(g) * kSegLZ;
+                G.len = std::min<uint32_t>(kSegLZ, blen - g * kSegLZ);
+                G.rem = blen - g * kSegLZ;
+                segs[kg + g] = G;
+            }
+            kg += nseg;
+        }
+        bsp[0] = 0;
+        bsp[1] = uint32_t(nsp);
+        if (kg != ng || ks != nsp) return CDC_E_INVALID;  // the counts and the plan disagree (a bug)
+    }
+    Batch Bt{};
+    Bt.base = static_cast<const uint8_t *>(d_in);
+    Bt.nblobs = 1;
+    Bt.nsegs = uint32_t(ng);
+    Bt.nblks = uint32_t(nk);
+    Bt.compress = 2;
+    Bt.blobs = reinterpret_cast<BlobDesc *>(ws + o_blobs);
+    Bt.segs = reinterpret_cast<Seg *>(ws + o_segs);
+    Bt.out = d_out;
+    Bt.out_cap = out_cap;
+    Bt.recs = reinterpret_cast<uint2 *>(ws + o_recs);
+    Bt.nrec = reinterpret_cast<uint32_t *>(ws + o_nrec);
+    Bt.trail = reinterpret_cast<uint32_t *>(ws + o_trail);
+    Bt.frame_len = reinterpret_cast<uint64_t *>(ws + o_flen);
+    Bt.out_off = reinterpret_cast<uint64_t *>(ws + o_oo);
+    Bt.status = reinterpret_cast<uint64_t *>(ws + o_status);
+    Bt.nspans = uint32_t(nsp);
+    Bt.spans = reinterpret_cast<Span *>(ws + o_spans);
+    Bt.blob_span0 = reinterpret_cast<uint32_t *>(ws + o_bsp);
+    Bt.sp = reinterpret_cast<SpanOut *>(ws + o_sp);
+    Bt.sp_lens = ws + o_splens;
+    Bt.sp_hdr = reinterpret_cast<uint32_t *>(ws + o_sphdr);
+    StreamArgs A{};
+    A.first = S->first ? 1u : 0u;
+    A.last = last ? 1u : 0u;
+    A.reg = S->reg;
+    A.isize = uint32_t(S->total + len);
+    A.res = reinterpret_cast<uint64_t *>(ws + o_res);
+    static_assert(sizeof(uint64_t) * 4 == 32, "status and res are read back together");
+    uint64_t back[4] = {0, 0, 0, 0};  // status[0..1], res[0..1]: consecutive 16-byte regions
+    bool ok = o_res == o_status + 16 && hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+        hipLaunchKernelGGL(k_dfl_size, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
+        hipLaunchKernelGGL(k_gzs_plan, dim3(1), dim3(64), 0, s, Bt, A);
+        hipLaunchKernelGGL(k_dfl_emit, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
+        hipLaunchKernelGGL(k_gzs_fin, dim3(1), dim3(64), 0, s, Bt, A);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(back, ws + o_status, sizeof(back), hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess;
+    }
+    if (!ok) return CDC_E_DEVICE;
+    *out_len = back[2];
+    if (back[0]) return int(int32_t(uint32_t(back[0])));  // CDC_E_NOSPACE: nothing written, the writer as it was
+    S->reg = infw::crc_mul(S->reg, infw::crc_shift(len)) ^ uint32_t(back[3]);
+    S->total += len;
+    S->first = false;
+    S->closed = last != 0;
+    return CDC_OK;
 }

@@ -41,6 +41,7 @@
 
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
+#include "cdc_locator.h"
 #include "restore_plan.h"
 
 namespace {
@@ -48,41 +49,7 @@ namespace {
 using Clock = std::chrono::steady_clock;
 static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
-struct Sum {
-    uint8_t b[32];
-    bool operator==(const Sum &o) const { return std::memcmp(b, o.b, 32) == 0; }
-};
-struct SumHash {  // the checksums are SHA-256: any eight bytes are a hash
-    size_t operator()(const Sum &s) const
-    {
-        uint64_t v;
-        std::memcpy(&v, s.b, 8);
-        return size_t(v);
-    }
-};
-struct Pack {
-    const uint8_t *mem;  // the caller's buffer, or NULL: read from path
-    std::string path;
-    uint64_t len;
-};
-struct Loc {
-    uint32_t pack, offset, length;
-};
-
-static void sha_cb(const void *data, size_t n, uint8_t out[32]) { cdc::sha256(data, n, out); }
-
-static bool pread_all(int fd, uint8_t *dst, uint64_t len, uint64_t off)
-{
-    while (len) {
-        const ssize_t r = pread(fd, dst, len, off_t(off));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        dst += r;
-        off += uint64_t(r);
-        len -= uint64_t(r);
-    }
-    return true;
-}
+using cdc::pread_all;
 
 static bool pwrite_all(int fd, const uint8_t *src, uint64_t len, uint64_t off)
 {
@@ -132,10 +99,7 @@ struct cdc_restore {
     int device = 0;
     cdc_restore_opts o{};
     std::vector<uint8_t> key;
-    std::vector<Pack> packs;
-    std::unordered_map<Sum, uint32_t, SumHash> index;  // checksum -> blob id
-    std::vector<Loc> locs;                             // by blob id
-    std::vector<Sum> sums;                             // by blob id
+    cdc::Locator loc;  // the registered packfiles: checksum -> blob id -> (packfile, offset, length)
     hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stages, download
     InSlot in[2];
     OutSlot out[2];
@@ -228,11 +192,11 @@ static void reader_stage(Run &X)
         uint64_t total = 0;
         std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
         for (size_t b = 0; b < nb; ++b) {
-            const Loc &L = R->locs[B.blobs[b].id];
+            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
             S.eoff[b] = total;
             S.elen[b] = L.length;
             total += L.length;
-            const Pack &P = R->packs[L.pack];
+            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
             if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
         }
         if (!S.h.reserve(total) || !S.d.reserve(total)) {
@@ -242,8 +206,8 @@ static void reader_stage(Run &X)
         }
         uint8_t *const h = S.h.as<uint8_t>();
         parallel_for(R->o.writers, nb, [&](size_t b) {
-            const Loc &L = R->locs[B.blobs[b].id];
-            const Pack &P = R->packs[L.pack];
+            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
+            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
             if (P.mem) {
                 std::memcpy(h + S.eoff[b], P.mem + L.offset, L.length);
                 return;
@@ -286,7 +250,7 @@ static void device_stage(Run &X)
         bst.assign(std::max<uint32_t>(nb, 1), CDC_OK);
         if (R->o.verify) {
             want.resize(size_t(nb) * 32 + 1);
-            for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], R->sums[B.blobs[b].id].b, 32);
+            for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], R->loc.sums[B.blobs[b].id].b, 32);
         }
         for (uint32_t b = 0; b < nb; ++b)
             if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
@@ -444,10 +408,10 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
         const cdc_restore_file &F = files[i];
         std::vector<uint32_t> ids(size_t(F.nchunks));
         for (uint64_t c = 0; c < F.nchunks; ++c) {
-            Sum s;
+            cdc::Sum s;
             std::memcpy(s.b, F.checksums + 32 * c, 32);
-            const auto it = R->index.find(s);
-            if (it == R->index.end()) {
+            const auto it = R->loc.index.find(s);
+            if (it == R->loc.index.end()) {
                 X.fstatus[i].store(CDC_E_NOTFOUND);
                 break;
             }
@@ -461,7 +425,7 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     for (size_t p = 0; p < X.pidx.size(); ++p)
         X.pf.push_back(rplan::File{files[X.pidx[p]].nchunks, X.fblob[p].data(), files[X.pidx[p]].lengths});
     rplan::plan(X.pf.data(), X.pf.size(), R->o.batch_bytes, X.batches);
-    std::vector<bool> used(R->locs.size(), false);
+    std::vector<bool> used(R->loc.locs.size(), false);
     for (const rplan::Batch &B : X.batches) {
         X.st.bytes += B.out_bytes;
         X.st.segments += B.segs.size();
@@ -517,22 +481,6 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     return X.fail;
 }
 
-static int add_rows(cdc_restore *R, Pack &&P, const std::vector<cdc_packfile_row> &rows)
-{
-    const uint32_t pack = uint32_t(R->packs.size());
-    R->packs.push_back(std::move(P));
-    for (const cdc_packfile_row &r : rows) {
-        if (r.type != rplan::kTypeChunk) continue;
-        Sum s;
-        std::memcpy(s.b, r.checksum, 32);
-        if (R->index.emplace(s, uint32_t(R->locs.size())).second) {
-            R->locs.push_back(Loc{pack, r.offset, r.length});
-            R->sums.push_back(s);
-        }
-    }
-    return CDC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -542,7 +490,7 @@ int cdc_packfile_index(const uint8_t *bytes, uint64_t len, cdc_packfile_footer *
 {
     if (!footer || (!bytes && len) || (!rows && cap)) return CDC_E_INVALID;
     if (needed) *needed = 0;
-    const int st = rplan::parse_packfile(bytes, len, sha_cb, footer, rows, cap);
+    const int st = rplan::parse_packfile(bytes, len, cdc::Locator::sha, footer, rows, cap);
     if (st != CDC_OK) return st;
     if (needed) *needed = footer->count;
     return footer->count > cap ? CDC_E_NOSPACE : CDC_OK;
@@ -589,13 +537,7 @@ int cdc_restore_add_packfile(cdc_restore *r, const uint8_t *bytes, uint64_t len)
     if (!r || (!bytes && len)) return CDC_E_INVALID;
     std::lock_guard<std::mutex> lk(r->run_mu);
     try {
-        cdc_packfile_footer f;
-        int st = rplan::parse_packfile(bytes, len, sha_cb, &f, nullptr, 0);
-        if (st != CDC_OK) return st;
-        std::vector<cdc_packfile_row> rows(f.count);
-        st = rplan::parse_packfile(bytes, len, sha_cb, &f, rows.data(), rows.size());
-        if (st != CDC_OK) return st;
-        return add_rows(r, Pack{bytes, std::string(), len}, rows);
+        return r->loc.add_memory(bytes, len);
     } catch (...) {
         return CDC_E_NOMEM;
     }
@@ -605,34 +547,11 @@ int cdc_restore_add_packfile_path(cdc_restore *r, const char *path)
 {
     if (!r || !path) return CDC_E_INVALID;
     std::lock_guard<std::mutex> lk(r->run_mu);
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return CDC_E_IO;
-    int st = CDC_OK;
     try {
-        struct stat sb;
-        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-            st = CDC_E_IO;
-        } else if (uint64_t(sb.st_size) < rplan::kFooterBytes) {
-            st = CDC_E_CORRUPT;
-        } else {
-            const uint64_t len = uint64_t(sb.st_size);
-            uint8_t tail[rplan::kFooterBytes];
-            cdc_packfile_footer f;
-            if (!pread_all(fd, tail, sizeof(tail), len - sizeof(tail))) st = CDC_E_IO;
-            if (st == CDC_OK) st = rplan::parse_footer(tail, len, &f);
-            if (st == CDC_OK) {
-                std::vector<uint8_t> idx(size_t(rplan::kRowBytes * f.count) + 1);
-                std::vector<cdc_packfile_row> rows(f.count);
-                if (!pread_all(fd, idx.data(), rplan::kRowBytes * f.count, f.index_offset)) st = CDC_E_IO;
-                if (st == CDC_OK) st = rplan::parse_index(idx.data(), f, sha_cb, rows.data(), rows.size());
-                if (st == CDC_OK) st = add_rows(r, Pack{nullptr, std::string(path), len}, rows);
-            }
-        }
+        return r->loc.add_path(path);
     } catch (...) {
-        st = CDC_E_NOMEM;
+        return CDC_E_NOMEM;
     }
-    close(fd);
-    return st;
 }
 
 int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,

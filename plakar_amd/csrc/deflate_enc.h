@@ -492,6 +492,42 @@ DFL_HD uint32_t choose_block(uint64_t P, uint32_t len, uint32_t fixed_bits, uint
 // zlib writes at level 0 for any length (an empty blob's 23 bytes included).
 DFL_HD uint64_t member_bound(uint64_t len) { return len + 18 + 5 * ((len + kSpan - 1) / kSpan + 1); }
 
+// ---- the stream form ----------------------------------------------------------------------------
+// One member written piece by piece (cdc_gzip_stream_piece): a piece's blocks
+// all have BFINAL clear, and an empty stored block after them (the joiner: 000,
+// zeros to the byte boundary, LEN 0, NLEN ffff) ends the piece on a byte
+// boundary, so the next piece starts at bit 0.  The last piece then adds the
+// final empty stored block (01 00 00 ff ff), as Go's compress/flate writes on
+// Close, before the member's CRC-32 and ISIZE.
+DFL_HD uint64_t joiner_bits(uint64_t P) { return stored_bits(P, 0); }
+constexpr uint32_t kFinalBytes = 5;
+
+// The joiner where the piece's last block ended: o is the byte that holds that
+// bit, sh the bit's place in it (0: a new byte) and edge the block's bits
+// there.  With `final` the final block follows.  Returns the bytes written
+// from o, the shared byte included: 5, or 6 from bit 6 on, and kFinalBytes more.
+DFL_HD uint32_t stream_end(uint8_t *o, uint32_t edge, uint32_t sh, bool final)
+{
+    const uint32_t a = (sh + 3 + 7) >> 3;  // bytes up to LEN: the shared or new one, and one more from bit 6 on
+    o[0] = uint8_t(sh ? edge & ((1u << sh) - 1u) : 0u);
+    if (a > 1) o[1] = 0;
+    o[a] = o[a + 1] = 0;
+    o[a + 2] = o[a + 3] = 0xFF;
+    uint32_t n = a + 4;
+    if (final) {
+        o[n] = 1;
+        o[n + 1] = o[n + 2] = 0;
+        o[n + 3] = o[n + 4] = 0xFF;
+        n += kFinalBytes;
+    }
+    return n;
+}
+
+// The most one piece of len bytes writes: the ten header bytes (first piece),
+// len and 5 bytes per span as in member_bound, 6 for the joiner, and the final
+// block, CRC-32 and ISIZE (last piece).
+DFL_HD uint64_t stream_piece_bound(uint64_t len) { return 10 + len + 5 * ((len + kSpan - 1) / kSpan) + 6 + kFinalBytes + 8; }
+
 // ---- packing ----------------------------------------------------------------------------------
 struct Codes {
     uint16_t lcode[kLitSlots], dcode[kDistSlots];
