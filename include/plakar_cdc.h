@@ -212,6 +212,54 @@ int cdc_gzip_stream_piece(cdc_gzip_stream *s, const void *d_in, uint64_t len, in
                           uint64_t out_cap, uint64_t *out_len, void *stream);
 void cdc_gzip_stream_free(cdc_gzip_stream *s);
 
+/* ---- Many raw DEFLATE streams in one call (zip entries) --------------------------
+ * What compress/flate does under archive/zip's fileWriter
+ * (cmd/plakar/subcommands/archive/archive.go:194-245 through zip.Writer's
+ * CreateHeader, one flate.NewWriter per entry), for n pieces that lie in one
+ * device buffer, into one device output, back to back in piece order.  A piece
+ * is an entry of the zip or, for an entry that spans calls, one part of it:
+ *   - a piece starts at bit 0 and is DEFLATE blocks, one per 32-KiB span, as
+ *     cdc_encode_device's GZIP members hold them (no ten-byte header);
+ *   - `first`: the entry's local file header (hdr_len > 0 bytes at
+ *     hdr_arena + hdr_off, host memory) goes before the deflate bytes;
+ *   - `last`: the piece's last block carries BFINAL and the stream ends at the
+ *     next byte boundary; an entry with no bytes at all (first and last,
+ *     len 0) is 01 00 00 ff ff.  Then comes the data descriptor: 50 4b 07 08,
+ *     the entry's CRC-32 (crc_reg: the register over the entry before this
+ *     piece, from 0xFFFFFFFF), its compressed and uncompressed size
+ *     (csize_before, usize_before plus this piece), 4 bytes each, or 8 bytes
+ *     each when either is 0xFFFFFFFF or more (archive/zip's isZip64);
+ *   - a piece that is not last ends with an empty stored block (000, zeros to
+ *     the byte boundary, 00 00 ff ff), so the entry's next piece, in a later
+ *     call, continues the stream; an empty one writes no deflate bytes.
+ * Per piece the call reports where it lies in d_out (out_off, out_len, the
+ * header and descriptor included), its deflate bytes, its CRC-32 register from
+ * 0 (the caller's running register r becomes crc_mul(r, x^(8 len)) ^ crc_reg,
+ * as cdc_gzip_stream_piece keeps it) and whether the descriptor is the 64-bit
+ * one; *total is the sum of out_len.  CDC_E_NOSPACE when out_cap is smaller
+ * than *total: *total is still set, nothing is written.  A piece of 2 GiB or
+ * more is CDC_E_UNSUPPORTED; a first piece without a header, a header outside
+ * the arena or a piece outside [0, src_cap) is CDC_E_INVALID.  The call keeps a
+ * workspace of its own per device, is synchronous on `stream`, and calls on
+ * one device are serialised. */
+typedef struct cdc_zip_piece {
+    uint64_t src_off, len;     /* in d_src */
+    uint32_t first, last;
+    uint32_t hdr_off, hdr_len; /* in hdr_arena (first pieces) */
+    uint32_t crc_reg;          /* the entry's CRC-32 register before this piece (0xFFFFFFFF at its start) */
+    uint32_t reserved;         /* 0 */
+    uint64_t csize_before, usize_before;
+} cdc_zip_piece;
+typedef struct cdc_zip_piece_out {
+    uint64_t out_off, out_len; /* in d_out: header, deflate bytes, descriptor */
+    uint64_t deflate_len;
+    uint32_t crc_reg;          /* over this piece's bytes, from 0, no final inversion */
+    uint32_t zip64;            /* last pieces: the descriptor holds 8-byte sizes */
+} cdc_zip_piece_out;
+int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src_cap, const cdc_zip_piece *pieces, uint32_t n,
+                          const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out, uint64_t out_cap,
+                          cdc_zip_piece_out *outs, uint64_t *total, void *stream);
+
 /* ---- Decode: open the AES-256-GCM stream, then inflate (LZ4 or GZIP) -------------
  * (*Repository).Decode (repository/repository.go:186-210) of n encoded blobs
  * that sit in device memory at d_in + offsets[i], lens[i] bytes each:
@@ -699,6 +747,24 @@ int cdc_archive_add_packfile_path(cdc_archive *a, const char *path);
 int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path,
                     cdc_archive_data_fn on_data, cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats);
 void cdc_archive_free(cdc_archive *a);
+/* `plakar archive -format zip` (archive.go:194-245: zip.FileInfoHeader, Method
+ * = zip.Deflate, CreateHeader, io.Copy per file; directories are not written,
+ * archive.go:211-213).  A context in zip mode: checked as cdc_archive_new
+ * checks, except that opts->format is not read; add_packfile, run and free
+ * take it as they are.  The output is archive/zip's on a non-seekable writer:
+ * per file a local header (version 20, flags 0x0008 and 0x0800 for a UTF-8
+ * name that needs it, method 8, DOS time and date from mtime in UTC clamped to
+ * 1980..2107, zero CRC and sizes, the name without leading slashes, the
+ * extended-timestamp extra), one raw DEFLATE stream (cdc_zip_pieces_device)
+ * and a data descriptor; after the last entry the central directory (creator
+ * 0x0314, external attributes (0100000 | mode) << 16, bit 0 for a file without
+ * the owner-write bit; zip64 extras where a size or an offset needs them) and
+ * the end records.  A directory entry is accepted and reported CDC_OK but not
+ * written and not counted in stats->entries.  A name empty after trimming,
+ * with a NUL or over 65,535 bytes, or mode bits above 07777: CDC_E_INVALID.
+ * batch_bytes counts file bytes plus local headers; stats->stream_bytes is
+ * their sum, output_bytes the archive's size.  Failures as cdc_archive_run's. */
+int cdc_archive_new_zip(int device, const cdc_archive_opts *opts, cdc_archive **out);
 
 /* The library's host SHA-256 (x86 SHA extensions when the CPU has them;
  * force_scalar != 0 takes the portable path).  cdc_sha256_accelerated: 1 if

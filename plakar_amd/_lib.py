@@ -153,6 +153,18 @@ class cdc_archive_stats(ctypes.Structure):
                                                "d2h_s", "write_s", "wall_s")]
 
 
+class cdc_zip_piece(ctypes.Structure):
+    _fields_ = [("src_off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("first", ctypes.c_uint32),
+                ("last", ctypes.c_uint32), ("hdr_off", ctypes.c_uint32), ("hdr_len", ctypes.c_uint32),
+                ("crc_reg", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("csize_before", ctypes.c_uint64),
+                ("usize_before", ctypes.c_uint64)]
+
+
+class cdc_zip_piece_out(ctypes.Structure):
+    _fields_ = [("out_off", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("deflate_len", ctypes.c_uint64),
+                ("crc_reg", ctypes.c_uint32), ("zip64", ctypes.c_uint32)]
+
+
 CDC_ARCHIVE_TAR, CDC_ARCHIVE_TARGZ = 0, 1
 CDC_ARCHIVE_FILE, CDC_ARCHIVE_DIR = 0, 1
 ARCHIVE_DATA_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
@@ -260,6 +272,10 @@ SIGNATURES = {
     "cdc_gzip_stream_piece": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
     "cdc_gzip_stream_free": (None, [ctypes.c_void_p]),
+    "cdc_zip_pieces_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(cdc_zip_piece),
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_uint64, _P(cdc_zip_piece_out), _P(ctypes.c_uint64),
+                                             ctypes.c_void_p]),
     "cdc_decode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
                                          ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_void_p]),
@@ -287,6 +303,7 @@ SIGNATURES = {
     "cdc_restore_free": (None, [ctypes.c_void_p]),
     "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
     "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
+    "cdc_archive_new_zip": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_archive_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "cdc_archive_run": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_archive_entry), ctypes.c_int, ctypes.c_char_p,

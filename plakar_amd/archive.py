@@ -1,12 +1,16 @@
 """Archive on the device: the byte path of `plakar archive`
-(cmd/plakar/subcommands/archive/archive.go) for its tar and tarball formats.
+(cmd/plakar/subcommands/archive/archive.go) for its tar, tarball and zip formats.
 The reference reads each file chunk by chunk, copies the bytes into an
 archive/tar writer and pushes the tar stream through one gzip.NewWriter.
 cdc_archive_run plans the tar stream in batches, decodes every distinct blob
 of a batch once, assembles header blocks, chunk occurrences and padding into
 the batch's image of the stream on the device, and for tarball deflates it
-there: GzipStream writes one gzip member out of many device pieces.  Every
-call goes through the C ABI (cdc_gzip_stream_*, cdc_archive_*)."""
+there: GzipStream writes one gzip member out of many device pieces.  For zip
+(ZipSession, zip_files) a batch's image holds only file bytes, every entry of
+the batch is deflated as its own raw stream in one call (zip_pieces_device),
+the local headers and data descriptors are placed on the device and the host
+writes the central directory after the last batch.  Every call goes through the
+C ABI (cdc_gzip_stream_*, cdc_zip_pieces_device, cdc_archive_*)."""
 import ctypes
 import os
 
@@ -119,6 +123,9 @@ class ArchiveSession:
         code = _lib.compress_code(compression)
         if format not in FORMATS:
             raise ValueError(f"unsupported format {format!r} (tar and tarball are implemented)")
+        self._open("cdc_archive_new", key, code, FORMATS[format], verify, writers, batch_bytes, device)
+
+    def _open(self, constructor, key, code, format_code, verify, writers, batch_bytes, device):
         self._h = None
         self._keep = []
         keybuf = None
@@ -133,9 +140,9 @@ class ArchiveSession:
         o.compress = code
         o.key = ctypes.cast(keybuf, ctypes.c_void_p) if keybuf is not None else None
         o.verify, o.writers, o.batch_bytes = int(bool(verify)), int(writers), int(batch_bytes)
-        o.format = FORMATS[format]
+        o.format = format_code
         h = ctypes.c_void_p()
-        check(lib().cdc_archive_new(int(device), ctypes.byref(o), ctypes.byref(h)), "cdc_archive_new")
+        check(getattr(lib(), constructor)(int(device), ctypes.byref(o), ctypes.byref(h)), constructor)
         self._h = h
 
     def add_packfile(self, packfile):
@@ -226,6 +233,71 @@ class ArchiveSession:
             pass
 
 
+class ZipSession(ArchiveSession):
+    """A native archive context in zip mode (cdc_archive_new_zip): the
+    reference's third format.  add_packfile, run and close are
+    ArchiveSession's.  Directories among the entries are accepted and not
+    written, as the reference writes none; names lose their leading slashes."""
+
+    def __init__(self, key=None, compression="LZ4", verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+        self._h = None
+        self._keep = []
+        self._open("cdc_archive_new_zip", key, _lib.compress_code(compression), 0, verify, writers, batch_bytes, device)
+
+
+def zip_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", verify=True, writers=8,
+              batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+    """One zip archive through the native pipeline (a ZipSession for this call
+    only).  Returns (data, statuses, stats) as ArchiveSession.run; a
+    directory's status is 0 though nothing is written for it."""
+    with ZipSession(key, compression, verify, writers, batch_bytes, device) as s:
+        for p in packfiles:
+            s.add_packfile(p)
+        return s.run(entries, path, on_data)
+
+
+def zip_piece_bound(n, header_len=0):
+    """The most one piece of n input bytes writes: its header, n and 5 bytes
+    per 32-KiB span, the 6 of the longest joiner, the 24-byte descriptor."""
+    return int(header_len) + int(n) + 5 * (-(-int(n) // 32768)) + 6 + 24
+
+
+def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=None):
+    """cdc_zip_pieces_device: deflate the pieces, each a dict with off and len
+    (in the device tensor `src`, uint8), first, last, hdr_off and hdr_len (in
+    the bytes `headers`), crc_reg (default 0xFFFFFFFF), csize_before and
+    usize_before (default 0), into the device tensor `out`.  Returns (total,
+    outs): outs[i] a dict of out_off, out_len, deflate_len, crc_reg and zip64.
+    CdcError CDC_E_NOSPACE (its `total` the bytes needed) when out_cap
+    (default: all of `out`) is smaller; nothing is written then."""
+    import torch
+    ensure_init()
+    n = len(pieces)
+    pcs = (_lib.cdc_zip_piece * max(n, 1))()
+    for i, p in enumerate(pieces):
+        pcs[i].src_off, pcs[i].len = int(p["off"]), int(p["len"])
+        pcs[i].first, pcs[i].last = int(bool(p.get("first"))), int(bool(p.get("last")))
+        pcs[i].hdr_off, pcs[i].hdr_len = int(p.get("hdr_off", 0)), int(p.get("hdr_len", 0))
+        pcs[i].crc_reg = int(p.get("crc_reg", 0xFFFFFFFF))
+        pcs[i].csize_before, pcs[i].usize_before = int(p.get("csize_before", 0)), int(p.get("usize_before", 0))
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError("out_cap is larger than out")
+    headers = bytes(headers)
+    outs = (_lib.cdc_zip_piece_out * max(n, 1))()
+    total = ctypes.c_uint64()
+    st = stream if stream is not None else torch.cuda.current_stream(device)
+    rc = lib().cdc_zip_pieces_device(int(device), ctypes.c_void_p(src.data_ptr()), src.numel(), pcs, n, headers,
+                                     len(headers), ctypes.c_void_p(out.data_ptr()), cap, outs, ctypes.byref(total),
+                                     ctypes.c_void_p(st.cuda_stream))
+    if rc < 0:
+        err = _lib.CdcError(rc, "cdc_zip_pieces_device")
+        err.total = int(total.value)
+        raise err
+    fields = [name for name, _ in _lib.cdc_zip_piece_out._fields_]
+    return int(total.value), [{f: int(getattr(outs[i], f)) for f in fields} for i in range(n)]
+
+
 def archive_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", format="tarball",
                   verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0):
     """One archive through the native pipeline (an ArchiveSession for this call
@@ -237,4 +309,5 @@ def archive_files(entries, packfiles, path=None, on_data=None, key=None, compres
         return s.run(entries, path, on_data)
 
 
-__all__ = ["GzipStream", "gzip_stream_bound", "ArchiveEntry", "ArchiveSession", "archive_files", "DEFAULT_BATCH_BYTES"]
+__all__ = ["GzipStream", "gzip_stream_bound", "ArchiveEntry", "ArchiveSession", "archive_files", "ZipSession", "zip_files",
+           "zip_pieces_device", "zip_piece_bound", "DEFAULT_BATCH_BYTES"]

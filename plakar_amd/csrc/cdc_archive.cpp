@@ -1,4 +1,4 @@
-// cdc_archive_*: a snapshot's entries as one tar or tar.gz stream
+// cdc_archive_*: a snapshot's entries as one tar or tar.gz stream, or as a zip
 // (include/plakar_cdc.h, "archive").
 //
 // The reference (cmd/plakar/subcommands/archive/archive.go:125-190) reads each
@@ -20,6 +20,18 @@
 //   D2H       the image, or for tar.gz only the compressed bytes;
 //   write     to the path or to on_data, in stream order.
 //
+// A context from cdc_archive_new_zip writes the zip format instead
+// (archive.go:194-245; zip_plan.h has the container and its planner): a batch's
+// image holds only file bytes, and in the place of the deflate stage
+//
+//   deflate   cdc_zip_pieces_device: every entry of the batch (or the part of
+//             one that the batch holds) as its own raw DEFLATE stream, its
+//             local header before it and its data descriptor behind it;
+//
+// only the compressed bytes come back, and after the last batch the host
+// writes the central directory and the end records from what it kept per
+// entry (CRC-32, sizes, the local header's offset).
+//
 // The stages of one batch run one after the other on the calling thread and
 // batches do not overlap yet (restore's three-thread rotation is the model for
 // that step); every stage's seconds are in the stats.
@@ -39,6 +51,9 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "deflate_enc.h"
+#include "inflate_walk.h"
+#include "zip_plan.h"
 
 namespace {
 
@@ -70,6 +85,7 @@ constexpr uint64_t kMaxBatch = 1ull << 30;  // a batch's image is one gzip piece
 struct cdc_archive {
     int device = 0;
     cdc_archive_opts o{};
+    bool zip = false;  // cdc_archive_new_zip: o.format is not read
     std::vector<uint8_t> key;
     cdc::Locator loc;
     hipStream_t stream = nullptr;
@@ -98,8 +114,9 @@ struct Run {
     }
 };
 
-// One batch through every stage; CDC_OK or the run's failure (X.failed set when a blob is to blame).
-static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool last)
+// read, H2D, Decode (+ verify) and assemble: the batch's image in A->d_img.
+// CDC_OK or the run's failure (X.failed set when a blob is to blame).
+static int stage_image(Run &X, const aplan::Batch &B)
 {
     cdc_archive *A = X.A;
     const cdc::Locator &L = A->loc;
@@ -142,7 +159,7 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
         if (fd < 0 || !cdc::pread_all(fd, h + eoff[b], l.length, l.offset)) pre[b] = CDC_E_IO;
     });
     close_fds();
-    std::memcpy(h + h_arena, B.arena.data(), B.arena.size());
+    if (!B.arena.empty()) std::memcpy(h + h_arena, B.arena.data(), B.arena.size());
     X.st.read_s += since(t0);
     X.st.encoded_bytes += enc;
     // which entry a blob belongs to (its first use in the batch), for a failure's name
@@ -160,7 +177,8 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
     t0 = Clock::now();
     uint8_t *const plain = A->d_plain.as<uint8_t>();
     if ((enc && hipMemcpyAsync(A->d_in.data(), h, enc, hipMemcpyHostToDevice, s) != hipSuccess) ||
-        hipMemcpyAsync(plain + arena_base, h + h_arena, B.arena.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        (!B.arena.empty() &&
+         hipMemcpyAsync(plain + arena_base, h + h_arena, B.arena.size(), hipMemcpyHostToDevice, s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
         return CDC_E_DEVICE;
     X.st.h2d_s += since(t0);
@@ -201,7 +219,7 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
     }
     // assemble
     t0 = Clock::now();
-    {
+    if (!B.segs.empty()) {
         const size_t ns = B.segs.size();
         std::vector<uint64_t> so(ns), sl(ns), sd(ns);
         for (size_t i = 0; i < ns; ++i) {
@@ -216,6 +234,17 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
         if (hipStreamSynchronize(s) != hipSuccess) return CDC_E_DEVICE;
     }
     X.st.assemble_s += since(t0);
+    return CDC_OK;
+}
+
+// One batch through every stage; CDC_OK or the run's failure.
+static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool last)
+{
+    cdc_archive *A = X.A;
+    hipStream_t s = A->stream;
+    int st = stage_image(X, B);
+    if (st != CDC_OK) return st;
+    auto t0 = Clock::now();
     // deflate
     const uint8_t *d_src = A->d_img.as<uint8_t>();
     uint64_t out_len = B.out_bytes;
@@ -223,7 +252,7 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
         t0 = Clock::now();
         const uint64_t cap = cdc_gzip_stream_bound(B.out_bytes);
         if (!A->d_gz.reserve(cap)) return CDC_E_NOMEM;
-        const int st = cdc_gzip_stream_piece(gz, d_src, B.out_bytes, last ? 1 : 0, A->d_gz.as<uint8_t>(), cap, &out_len, s);
+        st = cdc_gzip_stream_piece(gz, d_src, B.out_bytes, last ? 1 : 0, A->d_gz.as<uint8_t>(), cap, &out_len, s);
         if (st != CDC_OK) return st;
         d_src = A->d_gz.as<uint8_t>();
         X.st.deflate_s += since(t0);
@@ -237,7 +266,7 @@ static int run_batch(Run &X, const aplan::Batch &B, cdc_gzip_stream *gz, bool la
     X.st.d2h_s += since(t0);
     // write
     t0 = Clock::now();
-    const int st = X.emit(A->h_out.as<uint8_t>(), out_len);
+    st = X.emit(A->h_out.as<uint8_t>(), out_len);
     X.st.write_s += since(t0);
     return st;
 }
@@ -328,6 +357,197 @@ static int run(cdc_archive *A, const cdc_archive_entry *entries, int n, const ch
     return finish(st);
 }
 
+// ---- zip ---------------------------------------------------------------------
+struct OpenEntry {   // an entry whose stream is not closed yet
+    uint32_t reg = 0xFFFFFFFFu;  // CRC-32 register over its bytes so far
+    uint64_t csize = 0, usize = 0;
+};
+
+// The most a batch's pieces write: header, len and 5 bytes per span, the joiner's 6 (a last
+// piece's end is shorter), the 24-byte descriptor.
+static uint64_t zip_bound(const zplan::Batch &B)
+{
+    uint64_t cap = 0;
+    for (const zplan::Piece &P : B.pieces)
+        cap += P.hdr_len + P.len + 5 * ((P.len + dfl::kSpan - 1) / dfl::kSpan) + 6 + 24;
+    return cap;
+}
+
+// One zip batch: the image (file bytes only), every piece deflated in one call,
+// D2H of the compressed bytes, write; then the host's share: running CRC-32 and
+// sizes of the open entry, a directory record per entry that ends here.
+static int run_zip_batch(Run &X, const zplan::Batch &B, std::vector<zplan::Record> &recs, OpenEntry &open, uint64_t &stream_off)
+{
+    cdc_archive *A = X.A;
+    hipStream_t s = A->stream;
+    int st = stage_image(X, B.a);
+    if (st != CDC_OK) return st;
+    // deflate
+    auto t0 = Clock::now();
+    const size_t np = B.pieces.size();
+    std::vector<cdc_zip_piece> pc(np);
+    std::vector<cdc_zip_piece_out> po(np);
+    for (size_t i = 0; i < np; ++i) {
+        const zplan::Piece &P = B.pieces[i];
+        cdc_zip_piece &p = pc[i];
+        p = cdc_zip_piece{};
+        p.src_off = P.img_off;
+        p.len = P.len;
+        p.first = P.first;
+        p.last = P.last;
+        p.hdr_off = P.hdr_off;
+        p.hdr_len = P.hdr_len;
+        // only a batch's first piece can continue an entry: every other one starts its own
+        p.crc_reg = P.first ? 0xFFFFFFFFu : open.reg;
+        p.csize_before = P.first ? 0 : open.csize;
+        p.usize_before = P.first ? 0 : open.usize;
+    }
+    const uint64_t cap = zip_bound(B);
+    uint64_t total = 0;
+    if (!A->d_gz.reserve(cap)) return CDC_E_NOMEM;
+    st = cdc_zip_pieces_device(A->device, A->d_img.data(), B.a.out_bytes, pc.data(), uint32_t(np), B.hdrs.data(), B.hdrs.size(),
+                               A->d_gz.as<uint8_t>(), cap, po.data(), &total, s);
+    if (st != CDC_OK) {
+        // a piece the pass cannot take (2 GiB or more): the entry is to blame
+        if (st == CDC_E_UNSUPPORTED)
+            for (const zplan::Piece &P : B.pieces)
+                if (P.len > dfl::kMaxBlob) {
+                    X.failed = X.pidx[P.entry];
+                    break;
+                }
+        return st;
+    }
+    X.st.deflate_s += since(t0);
+    for (size_t i = 0; i < np; ++i) {
+        const zplan::Piece &P = B.pieces[i];
+        if (P.first) {
+            open = OpenEntry();
+            recs[P.entry].offset = stream_off + po[i].out_off;
+        }
+        open.reg = infw::crc_mul(open.reg, infw::crc_shift(P.len)) ^ po[i].crc_reg;
+        open.csize += po[i].deflate_len;
+        open.usize += P.len;
+        if (P.last) {
+            zplan::Record &R = recs[P.entry];
+            R.crc = ~open.reg;
+            R.csize = open.csize;
+            R.usize = open.usize;
+        }
+    }
+    stream_off += total;
+    // D2H
+    t0 = Clock::now();
+    if (!A->h_out.reserve(total)) return CDC_E_NOMEM;
+    if (total && (hipMemcpyAsync(A->h_out.data(), A->d_gz.data(), total, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                  hipStreamSynchronize(s) != hipSuccess))
+        return CDC_E_DEVICE;
+    X.st.d2h_s += since(t0);
+    // write
+    t0 = Clock::now();
+    st = X.emit(A->h_out.as<uint8_t>(), total);
+    X.st.write_s += since(t0);
+    return st;
+}
+
+static int run_zip(cdc_archive *A, const cdc_archive_entry *entries, int n, const char *path, cdc_archive_data_fn on_data,
+                   cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats)
+{
+    const auto w0 = Clock::now();
+    Run X{};
+    X.A = A;
+    X.on_data = on_data;
+    X.ctx = ctx;
+    auto finish = [&](int st) {
+        X.st.failed_entry = st == CDC_OK ? -1 : X.failed;
+        X.st.wall_s = since(w0);
+        if (stats) {
+            X.st.struct_size = uint32_t(std::min<size_t>(stats->struct_size, sizeof(X.st)));
+            std::memcpy(stats, &X.st, X.st.struct_size);
+        }
+        return st;
+    };
+    // the locator, as for tar; a directory is accepted and not written (archive.go:211-213)
+    std::vector<std::vector<uint32_t>> fblob;
+    std::vector<std::vector<uint8_t>> hdrs;
+    std::vector<zplan::Record> recs;
+    std::vector<int> dirs;
+    for (int i = 0; i < n; ++i) {
+        const cdc_archive_entry &E = entries[i];
+        if (E.type == CDC_ARCHIVE_DIR) {
+            dirs.push_back(i);
+            continue;
+        }
+        std::vector<uint32_t> ids(size_t(E.nchunks));
+        bool found = true;
+        for (uint64_t c = 0; c < ids.size() && found; ++c) {
+            cdc::Sum s;
+            std::memcpy(s.b, E.checksums + 32 * c, 32);
+            const auto it = A->loc.index.find(s);
+            found = it != A->loc.index.end();
+            if (found) ids[size_t(c)] = it->second;
+        }
+        if (!found) {
+            ++X.st.skipped_entries;
+            if (on_entry) on_entry(ctx, i, CDC_E_NOTFOUND);
+            continue;
+        }
+        std::vector<uint8_t> h;
+        zplan::Record R;
+        const int st = zplan::build_local(zplan::Entry{E.name, std::strlen(E.name), E.mode, E.mtime}, h, R);
+        if (st != CDC_OK) {  // a name or mode no header can carry: nothing is written
+            X.failed = i;
+            if (on_entry) on_entry(ctx, i, st);
+            return finish(st);
+        }
+        fblob.push_back(std::move(ids));
+        hdrs.push_back(std::move(h));
+        recs.push_back(std::move(R));
+        X.pidx.push_back(i);
+    }
+    std::vector<aplan::File> pf;
+    for (size_t p = 0; p < X.pidx.size(); ++p)
+        pf.push_back(aplan::File{hdrs[p].data(), hdrs[p].size(), fblob[p].size(), fblob[p].data(), entries[X.pidx[p]].lengths});
+    std::vector<zplan::Batch> batches;
+    zplan::plan(pf.data(), pf.size(), A->o.batch_bytes, batches);
+    for (const zplan::Batch &B : batches) {
+        X.st.stream_bytes += B.used;
+        X.st.segments += B.a.segs.size();
+        X.st.decoded_blobs += B.a.blobs.size();
+    }
+    X.st.batches = batches.size();
+    X.st.entries = X.pidx.size();
+    if (hipSetDevice(A->device) != hipSuccess) return finish(CDC_E_DEVICE);
+    if (path) {
+        X.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+        if (X.fd < 0) return finish(CDC_E_IO);
+    }
+    int st = CDC_OK;
+    OpenEntry open_entry;
+    uint64_t stream_off = 0;
+    for (size_t k = 0; k < batches.size() && st == CDC_OK; ++k) st = run_zip_batch(X, batches[k], recs, open_entry, stream_off);
+    if (st == CDC_OK) {
+        // the central directory and the end records, on the host
+        const auto t0 = Clock::now();
+        std::vector<uint8_t> tail;
+        zplan::build_tail(recs.data(), recs.size(), stream_off, tail);
+        st = X.emit(tail.data(), tail.size());
+        X.st.write_s += since(t0);
+    }
+    if (X.fd >= 0) {
+        if (close(X.fd) != 0 && st == CDC_OK) st = CDC_E_IO;
+        if (st != CDC_OK) unlink(path);
+    }
+    if (on_entry) {
+        if (st == CDC_OK) {
+            for (int i : X.pidx) on_entry(ctx, i, CDC_OK);
+            for (int i : dirs) on_entry(ctx, i, CDC_OK);
+        } else if (X.failed >= 0) {
+            on_entry(ctx, X.failed, st);
+        }
+    }
+    return finish(st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,6 +591,18 @@ int cdc_archive_new(int device, const cdc_archive_opts *opts, cdc_archive **out)
     return CDC_OK;
 }
 
+int cdc_archive_new_zip(int device, const cdc_archive_opts *opts, cdc_archive **out)
+{
+    if (!opts || !out) return CDC_E_INVALID;
+    *out = nullptr;
+    if (opts->struct_size != sizeof(*opts)) return CDC_E_INVALID;
+    cdc_archive_opts o = *opts;
+    o.format = CDC_ARCHIVE_TAR;  // the caller's is not read: zip is no value of it
+    const int st = cdc_archive_new(device, &o, out);
+    if (st == CDC_OK) (*out)->zip = true;
+    return st;
+}
+
 int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len)
 {
     if (!a || (!bytes && len)) return CDC_E_INVALID;
@@ -405,7 +637,7 @@ int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, con
     }
     std::lock_guard<std::mutex> lk(a->run_mu);
     try {
-        return run(a, entries, n, path, on_data, on_entry, ctx, stats);
+        return (a->zip ? run_zip : run)(a, entries, n, path, on_data, on_entry, ctx, stats);
     } catch (const std::bad_alloc &) {
         return CDC_E_NOMEM;
     }

@@ -69,18 +69,13 @@
 #include "cdc_internal.h"
 #include "cdc_crypto_dev.h"
 #include "cdc_hostmem.h"
+#include "cdc_encode_dev.h"  // Seg, Blk, BlobDesc, Span, SpanOut, Batch and the sizes they are planned with
 #include "deflate_enc.h"
 #include "inflate_walk.h"
 
 namespace enc {
 
 using namespace devc;
-
-constexpr uint32_t kSegLZ = 8192;             // LZ4 match-search segment
-constexpr uint64_t kBlockLZ = 4ull << 20;     // LZ4 block (pierrec Block4Mb)
-constexpr uint32_t kPiece = 65536;            // EncryptStream chunkSize
-constexpr uint32_t kHashBits = 11;
-constexpr uint32_t kRecCap = kSegLZ / 4 + 2;  // records per segment (a match per 4 bytes at most)
 
 // ---------------------------------------------------------------------------
 // AES tables, built on the host (FIPS-197: S-box = affine(inverse in GF(2^8))).
@@ -118,81 +113,6 @@ void build_tables(uint32_t te0[256], uint8_t sbox[256])  // cdc_decode.hip uploa
         te0[x] = uint32_t(mul(s, 2)) << 24 | uint32_t(s) << 16 | uint32_t(s) << 8 | mul(s, 3);
     }
 }
-
-struct Seg {             // an 8-KiB LZ4 search segment
-    uint64_t src;        // byte offset in the input base
-    uint32_t len;
-    uint32_t rem;        // bytes from the segment's start to its LZ4 block's end
-};
-
-struct Blk {             // a 4-MiB LZ4 block
-    uint64_t src;
-    uint32_t len, blob;
-    uint32_t seg0, nseg;
-    uint32_t k;          // block index in its blob
-    uint32_t pad;
-};
-
-struct BlobDesc {
-    uint64_t src;        // byte offset in the input base
-    uint64_t len;
-    uint64_t slot;       // frame slot in the frame buffer (16-B aligned)
-    uint32_t blk0, nblk;
-};
-
-struct Span {            // a DEFLATE span: up to dfl::kSpanSegs segments of one blob
-    uint64_t src;
-    uint32_t len, blob;
-    uint32_t seg0, nseg;
-    uint32_t k;          // span index in its blob
-    uint32_t last;       // the blob's last span: its block carries BFINAL
-};
-
-struct SpanOut {         // what the DEFLATE stages hand on, per span
-    uint32_t fixed_bits, dyn_bits;  // the whole block coded either way (k_dfl_size)
-    uint32_t hdr_bits;              // the dynamic header
-    uint32_t crc;                   // CRC-32 register over the span's bytes from 0, no final inversion
-    uint32_t type, nbits;           // the choice and the block's bits (k_enc_plan)
-    uint64_t bit;                   // where the block starts, in bits from the member's start
-    uint32_t edge_lo, edge_hi;      // its bits in the bytes it shares with its neighbours (k_dfl_emit)
-};
-
-constexpr uint32_t kSpanLens = dfl::kLitSlots + dfl::kDistSlots;  // code lengths kept per span
-
-struct Batch {
-    const uint8_t *base;
-    uint32_t nblobs, nsegs, nblks, npieces_max;
-    uint32_t compress, encrypt;
-    const BlobDesc *blobs;
-    const Seg *segs;
-    const Blk *blks;
-    const uint8_t *rnd;       // per blob: subkey 32, subkey nonce 12, data nonce 12
-    const uint8_t *key;       // repository key (32 B, device)
-    uint8_t *frames;          // frame buffer
-    uint8_t *out;
-    uint64_t out_cap;
-    // workspace
-    uint2 *recs;              // kRecCap per segment
-    uint32_t *nrec;           // per segment
-    uint32_t *trail;          // per segment: literals after its last match (from its start when none)
-    uint32_t *seg_out;        // per segment: bytes of its sequences in the block (k_lz4_size)
-    uint32_t *blk_size;       // per block: encoded size, bit 31 = stored raw
-    uint64_t *blk_foff;       // per block: offset of its header in the frame
-    uint32_t *xxh;            // per blob
-    uint64_t *frame_len;      // per blob
-    uint64_t *out_off;        // nblobs + 1
-    uint32_t *piece_base;     // nblobs + 1
-    BlobKey *keys;            // per blob
-    uint64_t *status;         // [0]: CDC_E_NOSPACE when out_cap is too small
-    const uint32_t *xx_ids;   // XXH32 order of the blobs
-    // GZIP (compress == 2)
-    uint32_t nspans;
-    const Span *spans;
-    const uint32_t *blob_span0;  // nblobs + 1
-    SpanOut *sp;
-    uint8_t *sp_lens;         // kSpanLens per span: literal/length then distance code lengths
-    uint32_t *sp_hdr;         // dfl::kHdrWords per span: the dynamic header's bits
-};
 
 // ---------------------------------------------------------------------------
 // XXH32 (the frame's content checksum): lanes 0-3 run accumulators v1..v4 over
@@ -320,7 +240,6 @@ __global__ __launch_bounds__(kXxWaves * 64) void k_xxh32(const Batch B)
 // match length), segment-relative; the literals before a match are the bytes
 // since the previous match's end.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kSeqWaves = 2;  // 12 KiB of LDS per wave (the segment and the hash table)
 constexpr uint32_t kSkipShift = 6;  // LZ4's skip trigger
 
 struct alignas(16) SeqLds {
@@ -1129,8 +1048,6 @@ __global__ __launch_bounds__(kGcmWaves * 64) void k_gcm(const Batch B)
 // code object and its time on C3 went from 224 to 259 us, the same
 // instructions.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kDflThreads = dfl::kStretches;
-static_assert(kDflThreads == 256 && dfl::kSeg == kSegLZ && kBlockLZ % dfl::kSpan == 0, "a span is four segments of one block");
 
 struct WgPar {
     uint32_t lane;
