@@ -179,7 +179,32 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
                       int compress, const uint8_t *key, const uint8_t *random, uint8_t *d_out, uint64_t out_cap,
                       uint64_t *out_offsets, void *stream);
 
+/* The compression level: compression.Configuration carries a Level beside the
+ * algorithm (compression/compression.go:12-51), and the reference's GZIP is
+ * flate level 6, a 32-KiB window.  Here the level chooses the match search:
+ *   CDC_LEVEL_FAST (0): matches inside their 8-KiB segment (what
+ *     cdc_encode_device writes);
+ *   CDC_LEVEL_WIDE (1): a match may also copy from up to 32,768 bytes before
+ *     its segment, never from before its 4-MiB block (LZ4's blocks stay
+ *     independent; DEFLATE uses the same floor) nor from before its blob, piece
+ *     or zip entry.  Smaller output, a slower search; the formats, the bounds
+ *     and every reader are the same.
+ * Every other value is CDC_E_INVALID; with CDC_COMPRESS_NONE the level changes
+ * nothing.  cdc_transcode_device's re-encode and cdc_backup_run stay at
+ * CDC_LEVEL_FAST. */
+#define CDC_LEVEL_FAST 0
+#define CDC_LEVEL_WIDE 1
+
+/* cdc_encode_device at `level` (compression/compression.go:12-51): the level
+ * changes which matches the LZ4 frame's sequences or the gzip member's blocks
+ * hold, so the bytes and their count, nothing else.  cdc_encode_device is this
+ * call with CDC_LEVEL_FAST. */
+int cdc_encode_device_level(int device, const void *d_base, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                            int compress, const uint8_t *key, const uint8_t *random, uint8_t *d_out, uint64_t out_cap,
+                            uint64_t *out_offsets, int level, void *stream);
+
 /* Upper bound of one blob's encoding (for out_cap); `compress` is the selector.
+ * It holds at either level.
  * GZIP: len + 18 + 5 * (ceil(len / 32768) + 1) before encryption (a span is
  * coded only when that is no larger than storing it). */
 uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt);
@@ -211,6 +236,11 @@ uint64_t cdc_gzip_stream_bound(uint64_t len);
 int cdc_gzip_stream_piece(cdc_gzip_stream *s, const void *d_in, uint64_t len, int last, uint8_t *d_out,
                           uint64_t out_cap, uint64_t *out_len, void *stream);
 void cdc_gzip_stream_free(cdc_gzip_stream *s);
+/* The level of the member's match search (compression/compression.go:12-51;
+ * CDC_LEVEL_* above): with CDC_LEVEL_WIDE a match reaches up to 32,768 bytes
+ * back inside its piece, never into the piece before.  A member is written at
+ * one level: CDC_E_INVALID once a piece has been written.  The bound holds. */
+int cdc_gzip_stream_set_level(cdc_gzip_stream *s, int level);
 
 /* ---- Many raw DEFLATE streams in one call (zip entries) --------------------------
  * What compress/flate does under archive/zip's fileWriter
@@ -259,6 +289,13 @@ typedef struct cdc_zip_piece_out {
 int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src_cap, const cdc_zip_piece *pieces, uint32_t n,
                           const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out, uint64_t out_cap,
                           cdc_zip_piece_out *outs, uint64_t *total, void *stream);
+/* cdc_zip_pieces_device at `level` (compression/compression.go:12-51; CDC_LEVEL_*
+ * above): with CDC_LEVEL_WIDE a match reaches up to 32,768 bytes back inside
+ * its piece, never into another piece.  cdc_zip_pieces_device is this call
+ * with CDC_LEVEL_FAST. */
+int cdc_zip_pieces_device_level(int device, const void *d_src, uint64_t src_cap, const cdc_zip_piece *pieces, uint32_t n,
+                                const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out, uint64_t out_cap,
+                                cdc_zip_piece_out *outs, uint64_t *total, int level, void *stream);
 
 /* ---- Decode: open the AES-256-GCM stream, then inflate (LZ4 or GZIP) -------------
  * (*Repository).Decode (repository/repository.go:186-210) of n encoded blobs
@@ -543,6 +580,11 @@ int cdc_backup_new(int device, const cdc_backup_opts *opts, cdc_backup **out);
 int cdc_backup_files(cdc_backup *b, const char *const *paths, int n, cdc_backup_file_fn on_file,
                      cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats);
 void cdc_backup_free(cdc_backup *b);
+/* The level Encode runs at in later cdc_backup_files calls of this session
+ * (compression/compression.go:12-51; CDC_LEVEL_* above): CDC_LEVEL_WIDE stores
+ * smaller LZ4 or GZIP blobs.  A run in progress keeps the level it began with.
+ * cdc_backup_run has no session and stays at CDC_LEVEL_FAST. */
+int cdc_backup_set_level(cdc_backup *b, int level);
 /* new + files + free in one call. */
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
                    cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats);
@@ -747,6 +789,11 @@ int cdc_archive_add_packfile_path(cdc_archive *a, const char *path);
 int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path,
                     cdc_archive_data_fn on_data, cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats);
 void cdc_archive_free(cdc_archive *a);
+/* The level of later cdc_archive_run calls (compression/compression.go:12-51;
+ * CDC_LEVEL_* above): the gzip member of a tar.gz and the entries of a zip
+ * (cdc_archive_new_zip) are deflated with the wide match search; a plain tar
+ * is not compressed and does not change. */
+int cdc_archive_set_level(cdc_archive *a, int level);
 /* `plakar archive -format zip` (archive.go:194-245: zip.FileInfoHeader, Method
  * = zip.Deflate, CreateHeader, io.Copy per file; directories are not written,
  * archive.go:211-213).  A context in zip mode: checked as cdc_archive_new

@@ -39,6 +39,18 @@ CDC_COMPRESS_NONE = 0
 CDC_COMPRESS_LZ4 = 1
 CDC_COMPRESS_GZIP = 2
 
+# the compression level (compression.Configuration.Level, compression/compression.go:12-51): which
+# match search Encode, the gzip stream, the zip pieces and the archive and backup sessions run
+CDC_LEVEL_FAST = 0  # matches inside their 8-KiB segment
+CDC_LEVEL_WIDE = 1  # matches from up to 32 KiB before the segment
+
+
+def level_code(level):
+    """The C level for 0 / 1 (CDC_LEVEL_FAST / CDC_LEVEL_WIDE); ValueError otherwise."""
+    if isinstance(level, bool) or level not in (CDC_LEVEL_FAST, CDC_LEVEL_WIDE):
+        raise ValueError(f"unsupported level {level!r} (0: fast, 1: wide)")
+    return int(level)
+
 
 def compress_code(compression):
     """The selector for a repository's compression name ("LZ4", "GZIP" or None)."""
@@ -266,16 +278,25 @@ SIGNATURES = {
     "cdc_encode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                          ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
+    "cdc_encode_device_level": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
+                                               ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
+                                               ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_int,
+                                               ctypes.c_void_p]),
     "cdc_encode_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int]),
     "cdc_gzip_stream_new": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_void_p)]),
     "cdc_gzip_stream_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
     "cdc_gzip_stream_piece": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_void_p]),
     "cdc_gzip_stream_free": (None, [ctypes.c_void_p]),
+    "cdc_gzip_stream_set_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cdc_zip_pieces_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(cdc_zip_piece),
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                              ctypes.c_uint64, _P(cdc_zip_piece_out), _P(ctypes.c_uint64),
                                              ctypes.c_void_p]),
+    "cdc_zip_pieces_device_level": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(cdc_zip_piece),
+                                                   ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_uint64, _P(cdc_zip_piece_out), _P(ctypes.c_uint64),
+                                                   ctypes.c_int, ctypes.c_void_p]),
     "cdc_decode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
                                          ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_void_p]),
@@ -309,6 +330,7 @@ SIGNATURES = {
     "cdc_archive_run": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_archive_entry), ctypes.c_int, ctypes.c_char_p,
                                        ARCHIVE_DATA_FN, ARCHIVE_ENTRY_FN, ctypes.c_void_p, _P(cdc_archive_stats)]),
     "cdc_archive_free": (None, [ctypes.c_void_p]),
+    "cdc_archive_set_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cdc_set_debug_mode": (ctypes.c_int, [ctypes.c_int]),
     "cdc_gear_is_placeholder": (ctypes.c_int, []),
     "cdc_set_maskl_index_mode": (ctypes.c_int, [ctypes.c_int]),
@@ -318,6 +340,7 @@ SIGNATURES = {
     "cdc_backup_files": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_char_p), ctypes.c_int, BACKUP_FILE_FN,
                                         BACKUP_PACK_FN, ctypes.c_void_p, _P(cdc_backup_stats)]),
     "cdc_backup_free": (None, [ctypes.c_void_p]),
+    "cdc_backup_set_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cdc_sha256": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, _P(ctypes.c_uint8)]),
     "cdc_sha256_accelerated": (ctypes.c_int, []),
     "cdc_chunk_entropy_device_async": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,

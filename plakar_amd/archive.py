@@ -34,14 +34,25 @@ class GzipStream:
     concatenated, are what gzip.NewWriter(out) ... Close() gives for the
     concatenated inputs (any inflater reads them as one member).  Every
     piece ends on a byte boundary; the piece given with last=True closes the
-    member (CRC-32 of the whole stream, ISIZE mod 2^32)."""
+    member (CRC-32 of the whole stream, ISIZE mod 2^32).  `level`: 0, or 1
+    for matches from up to 32 KiB back inside a piece (set_level changes it
+    until the first piece is written)."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, level=0):
         import torch  # noqa: F401  (torch's HIP runtime comes up before the library's)
+        level = _lib.level_code(level)
         ensure_init()
         self.device = device
         self._h = ctypes.c_void_p()
         check(lib().cdc_gzip_stream_new(int(device), ctypes.byref(self._h)), "cdc_gzip_stream_new")
+        if level:
+            self.set_level(level)
+
+    def set_level(self, level):
+        """cdc_gzip_stream_set_level: CdcError CDC_E_INVALID once a piece has been written."""
+        if not self._h:
+            raise ValueError("the stream is closed")
+        check(lib().cdc_gzip_stream_set_level(self._h, _lib.level_code(level)), "cdc_gzip_stream_set_level")
 
     def close(self):
         if self._h:
@@ -116,18 +127,20 @@ class ArchiveSession:
     """A native archive context (cdc_archive_new): the repository's Decode
     configuration (compression "LZ4", "GZIP" or None, the 32-byte key or
     None), the output format ("tar", or "tarball": tar.gz, the reference's
-    default) and the registered packfiles."""
+    default) and the registered packfiles.  `level`: the match search of the
+    tar.gz member (0, or 1: a 32-KiB window; cdc_archive_set_level)."""
 
     def __init__(self, key=None, compression="LZ4", format="tarball", verify=True, writers=8,
-                 batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+                 batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):
         code = _lib.compress_code(compression)
         if format not in FORMATS:
             raise ValueError(f"unsupported format {format!r} (tar and tarball are implemented)")
-        self._open("cdc_archive_new", key, code, FORMATS[format], verify, writers, batch_bytes, device)
+        self._open("cdc_archive_new", key, code, FORMATS[format], verify, writers, batch_bytes, device, level)
 
-    def _open(self, constructor, key, code, format_code, verify, writers, batch_bytes, device):
+    def _open(self, constructor, key, code, format_code, verify, writers, batch_bytes, device, level=0):
         self._h = None
         self._keep = []
+        level = _lib.level_code(level)
         keybuf = None
         if key is not None:
             key = bytes(key)
@@ -144,6 +157,8 @@ class ArchiveSession:
         h = ctypes.c_void_p()
         check(getattr(lib(), constructor)(int(device), ctypes.byref(o), ctypes.byref(h)), constructor)
         self._h = h
+        if level:
+            check(lib().cdc_archive_set_level(h, level), "cdc_archive_set_level")
 
     def add_packfile(self, packfile):
         """Register a packfile: bytes (kept alive by the session) or a path."""
@@ -237,20 +252,23 @@ class ZipSession(ArchiveSession):
     """A native archive context in zip mode (cdc_archive_new_zip): the
     reference's third format.  add_packfile, run and close are
     ArchiveSession's.  Directories among the entries are accepted and not
-    written, as the reference writes none; names lose their leading slashes."""
+    written, as the reference writes none; names lose their leading slashes.
+    `level`: the match search of the entries' DEFLATE streams, as ArchiveSession's."""
 
-    def __init__(self, key=None, compression="LZ4", verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+    def __init__(self, key=None, compression="LZ4", verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0,
+                 level=0):
         self._h = None
         self._keep = []
-        self._open("cdc_archive_new_zip", key, _lib.compress_code(compression), 0, verify, writers, batch_bytes, device)
+        self._open("cdc_archive_new_zip", key, _lib.compress_code(compression), 0, verify, writers, batch_bytes, device,
+                   level)
 
 
 def zip_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", verify=True, writers=8,
-              batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+              batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):
     """One zip archive through the native pipeline (a ZipSession for this call
     only).  Returns (data, statuses, stats) as ArchiveSession.run; a
     directory's status is 0 though nothing is written for it."""
-    with ZipSession(key, compression, verify, writers, batch_bytes, device) as s:
+    with ZipSession(key, compression, verify, writers, batch_bytes, device, level) as s:
         for p in packfiles:
             s.add_packfile(p)
         return s.run(entries, path, on_data)
@@ -262,15 +280,18 @@ def zip_piece_bound(n, header_len=0):
     return int(header_len) + int(n) + 5 * (-(-int(n) // 32768)) + 6 + 24
 
 
-def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=None):
+def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=None, level=0):
     """cdc_zip_pieces_device: deflate the pieces, each a dict with off and len
     (in the device tensor `src`, uint8), first, last, hdr_off and hdr_len (in
     the bytes `headers`), crc_reg (default 0xFFFFFFFF), csize_before and
     usize_before (default 0), into the device tensor `out`.  Returns (total,
     outs): outs[i] a dict of out_off, out_len, deflate_len, crc_reg and zip64.
     CdcError CDC_E_NOSPACE (its `total` the bytes needed) when out_cap
-    (default: all of `out`) is smaller; nothing is written then."""
+    (default: all of `out`) is smaller; nothing is written then.  `level`: 0,
+    or 1 for matches from up to 32 KiB back inside a piece
+    (cdc_zip_pieces_device_level)."""
     import torch
+    level = _lib.level_code(level)
     ensure_init()
     n = len(pieces)
     pcs = (_lib.cdc_zip_piece * max(n, 1))()
@@ -287,9 +308,12 @@ def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=
     outs = (_lib.cdc_zip_piece_out * max(n, 1))()
     total = ctypes.c_uint64()
     st = stream if stream is not None else torch.cuda.current_stream(device)
-    rc = lib().cdc_zip_pieces_device(int(device), ctypes.c_void_p(src.data_ptr()), src.numel(), pcs, n, headers,
-                                     len(headers), ctypes.c_void_p(out.data_ptr()), cap, outs, ctypes.byref(total),
-                                     ctypes.c_void_p(st.cuda_stream))
+    args = (int(device), ctypes.c_void_p(src.data_ptr()), src.numel(), pcs, n, headers, len(headers),
+            ctypes.c_void_p(out.data_ptr()), cap, outs, ctypes.byref(total))
+    if level:
+        rc = lib().cdc_zip_pieces_device_level(*args, level, ctypes.c_void_p(st.cuda_stream))
+    else:
+        rc = lib().cdc_zip_pieces_device(*args, ctypes.c_void_p(st.cuda_stream))
     if rc < 0:
         err = _lib.CdcError(rc, "cdc_zip_pieces_device")
         err.total = int(total.value)
@@ -299,11 +323,11 @@ def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=
 
 
 def archive_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", format="tarball",
-                  verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+                  verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):
     """One archive through the native pipeline (an ArchiveSession for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (data, statuses, stats) as ArchiveSession.run."""
-    with ArchiveSession(key, compression, format, verify, writers, batch_bytes, device) as s:
+    with ArchiveSession(key, compression, format, verify, writers, batch_bytes, device, level) as s:
         for p in packfiles:
             s.add_packfile(p)
         return s.run(entries, path, on_data)

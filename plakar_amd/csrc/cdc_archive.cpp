@@ -86,6 +86,7 @@ struct cdc_archive {
     int device = 0;
     cdc_archive_opts o{};
     bool zip = false;  // cdc_archive_new_zip: o.format is not read
+    int level = CDC_LEVEL_FAST;  // cdc_archive_set_level: the match search of tar.gz and zip
     std::vector<uint8_t> key;
     cdc::Locator loc;
     hipStream_t stream = nullptr;
@@ -342,6 +343,7 @@ static int run(cdc_archive *A, const cdc_archive_entry *entries, int n, const ch
     }
     cdc_gzip_stream *gz = nullptr;
     int st = A->o.format == CDC_ARCHIVE_TARGZ ? cdc_gzip_stream_new(A->device, &gz) : CDC_OK;
+    if (st == CDC_OK && gz) st = cdc_gzip_stream_set_level(gz, A->level);
     for (size_t k = 0; k < batches.size() && st == CDC_OK; ++k) st = run_batch(X, batches[k], gz, k + 1 == batches.size());
     cdc_gzip_stream_free(gz);
     if (X.fd >= 0) {
@@ -405,8 +407,8 @@ static int run_zip_batch(Run &X, const zplan::Batch &B, std::vector<zplan::Recor
     const uint64_t cap = zip_bound(B);
     uint64_t total = 0;
     if (!A->d_gz.reserve(cap)) return CDC_E_NOMEM;
-    st = cdc_zip_pieces_device(A->device, A->d_img.data(), B.a.out_bytes, pc.data(), uint32_t(np), B.hdrs.data(), B.hdrs.size(),
-                               A->d_gz.as<uint8_t>(), cap, po.data(), &total, s);
+    st = cdc_zip_pieces_device_level(A->device, A->d_img.data(), B.a.out_bytes, pc.data(), uint32_t(np), B.hdrs.data(),
+                                     B.hdrs.size(), A->d_gz.as<uint8_t>(), cap, po.data(), &total, A->level, s);
     if (st != CDC_OK) {
         // a piece the pass cannot take (2 GiB or more): the entry is to blame
         if (st == CDC_E_UNSUPPORTED)
@@ -601,6 +603,14 @@ int cdc_archive_new_zip(int device, const cdc_archive_opts *opts, cdc_archive **
     const int st = cdc_archive_new(device, &o, out);
     if (st == CDC_OK) (*out)->zip = true;
     return st;
+}
+
+int cdc_archive_set_level(cdc_archive *a, int level)
+{
+    if (!a || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(a->run_mu);
+    a->level = level;
+    return CDC_OK;
 }
 
 int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len)

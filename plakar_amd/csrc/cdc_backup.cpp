@@ -241,6 +241,7 @@ struct cdc_backup {
     // serialises them).
     hipStream_t stream[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int hw_queues = 0;  // GPU_MAX_HW_QUEUES at cdc_backup_new (0: unset)
+    std::atomic<int> level{CDC_LEVEL_FAST};  // cdc_backup_set_level: Encode's match search in later runs
 };
 
 namespace {
@@ -264,6 +265,7 @@ struct EncJob {
 struct Run {
     cdc_backup *B;
     const cdc_backup_opts &o;
+    const int level;  // the session's when the run began
     const char *const *paths;
     int n;
     cdc_backup_file_fn on_file;
@@ -316,7 +318,7 @@ struct Run {
         trace.push_back(Ev{t, what, batch, unit, bytes});
     }
 
-    Run(cdc_backup *b, const char *const *p, int nn) : B(b), o(b->o), paths(p), n(nn)
+    Run(cdc_backup *b, const char *const *p, int nn) : B(b), o(b->o), level(b->level.load()), paths(p), n(nn)
     {
         if (const char *f = std::getenv("CDC_BACKUP_FAIL_PIECE")) {
             long a = -1, c = -1;
@@ -952,8 +954,8 @@ int encode_job(Run &R, EncJob &J, hipStream_t se)
     std::vector<uint64_t> oo(nb + 1, 0);
     R.ev("encode", int64_t(J.k), -1, J.bound);
     const auto e0 = Clock::now();
-    st = cdc_encode_device(R.B->device, s.d_in, J.off.data(), J.len.data(), nb, R.o.compress, R.o.key,
-                           R.o.key ? rnd.data() : nullptr, s.d_enc, s.d_enc.cap(), oo.data(), se);
+    st = cdc_encode_device_level(R.B->device, s.d_in, J.off.data(), J.len.data(), nb, R.o.compress, R.o.key,
+                                 R.o.key ? rnd.data() : nullptr, s.d_enc, s.d_enc.cap(), oo.data(), R.level, se);
     if (st != CDC_OK) return st;
     const auto e1 = Clock::now();
     if (!s.h_enc.reserve(oo[nb], s.d_enc.cap())) return CDC_E_DEVICE;  // when it grows, to the bound at once
@@ -1185,6 +1187,13 @@ int cdc_backup_new(int device, const cdc_backup_opts *opts, cdc_backup **out)
         return CDC_E_DEVICE;
     }
     *out = b;
+    return CDC_OK;
+}
+
+int cdc_backup_set_level(cdc_backup *B, int level)
+{
+    if (!B || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    B->level.store(level);
     return CDC_OK;
 }
 

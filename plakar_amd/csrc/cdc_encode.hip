@@ -33,7 +33,10 @@
 //
 // Matches stay inside their 8-KiB segment, so compression ratios are those
 // of LZ4 with an 8-KiB window; any LZ4 decoder reads the frames (the tests
-// decode them with the system's liblz4).  Nonces and subkeys come from the
+// decode them with the system's liblz4).  At CDC_LEVEL_WIDE
+// (cdc_encode_device_level) k_lz_seq_wide runs in k_lz4_seq's place: the same
+// records, from a window that starts up to 32 KiB before the segment (Seg.hist)
+// and never before its 4-MiB block or its blob; every later kernel is the same.  Nonces and subkeys come from the
 // caller (the host fills them from the OS CSPRNG), as crypto/rand does in
 // the reference; piece k of a blob uses the blob's data nonce with its last
 // four bytes XOR k (big-endian), unique per subkey.
@@ -1087,6 +1090,7 @@ __device__ __forceinline__ dfl::SpanView span_view(const Batch &B, const Span &S
         const bool in = g < S.nseg;
         V.rec[g] = reinterpret_cast<const dfl::Rec *>(B.recs + uint64_t(S.seg0 + (in ? g : 0u)) * kRecCap);
         V.nrec[g] = in ? B.nrec[S.seg0 + g] : 0u;
+        V.hist[g] = in ? uint32_t(B.segs[S.seg0 + g].hist) : 0u;
     }
     V.len = S.len;
     return V;
@@ -1359,6 +1363,149 @@ __global__ __launch_bounds__(64) void k_gzs_fin(const Batch B, const StreamArgs 
 }
 
 // ---------------------------------------------------------------------------
+// k_lz_seq_wide (CDC_LEVEL_WIDE): k_lz4_seq's search with a window that starts
+// up to kWideHist bytes before the segment.  One wave per segment, one wave per
+// workgroup: the window (S.hist bytes of history, then the segment) and a hash
+// table of 16,384 u16 window positions in LDS, 72 KiB, two workgroups per CU.
+// Every history position enters the table before the first lookup (four per
+// lane and step from two words), so a repeat that starts anywhere in the
+// segment has its twin there whatever the stride.  A candidate more than
+// kWideHist back is refused by a compare; records, nrec and trail are
+// k_lz4_seq's, with offsets of up to hist + start.  It stands behind the GCM
+// kernels like the DEFLATE kernels.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kWideWin = kWideHist + kSegLZ;  // 40,960: the longest window
+constexpr uint32_t kWideHashBits = 14;
+
+struct alignas(16) WideLds {
+    uint32_t data[kWideWin / 4 + 4];  // the window and 16 zero bytes after it
+    uint16_t tab[1u << kWideHashBits];  // window position + 1 (0: empty)
+};
+static_assert(sizeof(WideLds) <= 160u * 1024u, "a workgroup's LDS");
+static_assert(kWideWin + 1 <= 0xFFFFu, "window positions fit u16");
+static_assert(kWideHist <= 0xFFFFu && kWideHist == dfl::kMaxDist, "the record's 16 offset bits; DEFLATE's distances");
+
+__device__ __forceinline__ uint32_t wide_rd32(const uint32_t *d, uint32_t p)  // bytes p..p+3 (any p)
+{
+    return __builtin_amdgcn_alignbit(d[(p >> 2) + 1], d[p >> 2], (p & 3u) * 8u);
+}
+
+__device__ __forceinline__ uint32_t wide_rd8(const uint32_t *d, uint32_t p) { return (d[p >> 2] >> ((p & 3u) * 8u)) & 255u; }
+
+__device__ __forceinline__ uint32_t wide_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kWideHashBits); }
+
+__global__ __launch_bounds__(64) void k_lz_seq_wide(const Batch B)
+{
+    __shared__ WideLds L;
+    const uint32_t lane = threadIdx.x, g = blockIdx.x;
+    if (g >= B.nsegs) return;
+    const Seg S = B.segs[g];
+    const uint32_t n = S.len, hist = min(uint32_t(S.hist), kWideHist), W = hist + n;  // W <= kWideWin
+    const uint8_t *win = B.base + S.src - hist;  // the plan keeps this inside the segment's block
+    // the window into LDS: whole 16-byte pieces by unaligned global loads, eight
+    // in flight per lane; the last partial piece byte by byte over zeros.
+    // Nothing before win or from win + W on is read.
+    const uint32_t nfull = W >> 4;
+    const uint32_t nbulk = nfull & ~511u;  // 8 KiB at a time, no lane left out: nothing between the loads and the stores
+    for (uint32_t i0 = 0; i0 < nbulk; i0 += 64 * 8) {
+        uint4 v[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) __builtin_memcpy(&v[j], win + 16 * (i0 + 64 * j + lane), 16);
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) *reinterpret_cast<uint4 *>(&L.data[4 * (i0 + 64 * j + lane)]) = v[j];
+    }
+    for (uint32_t i = nbulk + lane; i < nfull; i += 64) {  // a blob's last, short segment
+        uint4 v;
+        __builtin_memcpy(&v, win + 16 * i, 16);
+        *reinterpret_cast<uint4 *>(&L.data[4 * i]) = v;
+    }
+    const uint32_t tail = W & 15u;
+    if (lane < (tail ? 8u : 4u)) L.data[4 * nfull + lane] = 0;  // at most kWideWin / 4 + 4 words: a tail means W < kWideWin
+    for (uint32_t i = lane; i < (1u << kWideHashBits) / 8; i += 64) reinterpret_cast<uint4 *>(L.tab)[i] = make_uint4(0, 0, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < tail) reinterpret_cast<uint8_t *>(L.data)[16 * nfull + lane] = win[16 * nfull + lane];
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // every position of the history into the table, ascending, so a bucket
+    // keeps the latest (within one step of 256 positions whichever lane's
+    // write lands last: a candidate is verified, so any of them is sound).
+    // hist is a multiple of the segment size, so whole words cover it.
+    for (uint32_t j = lane; j < hist / 4; j += 64) {
+        const uint32_t w0 = L.data[j], w1 = L.data[j + 1];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t v = k ? __builtin_amdgcn_alignbit(w1, w0, 8 * k) : w0;
+            L.tab[wide_hash(v)] = uint16_t(4 * j + k + 1);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // LZ4's block rules as k_lz4_seq computes them, here in window positions
+    const uint32_t start_lim = hist + min(n >= 4 ? n - 3 : 0u, S.rem > 12 ? S.rem - 12 : 0u);
+    const uint32_t end_lim = hist + min(n, S.rem > 5 ? S.rem - 5 : 0u);
+    uint2 *rec = B.recs + uint64_t(g) * kRecCap;
+    uint32_t cursor = hist, anchor = hist, nrec = 0;
+    while (cursor < start_lim) {  // the cursor moves forward every turn: at most n turns
+        const uint32_t stride = 1u + ((cursor - anchor) >> kSkipShift);
+        const uint32_t p = cursor + lane * stride;
+        const bool valid = p < start_lim;
+        const uint32_t v = valid ? wide_rd32(L.data, p) : 0u;
+        const uint32_t h = wide_hash(v);
+        const uint32_t cand = valid ? L.tab[h] : 0u;
+        const uint32_t c = cand ? cand - 1 : 0u;
+        const bool ok = valid && cand != 0u && c < p && p - c <= kWideHist && wide_rd32(L.data, c) == v;
+        const uint64_t m = __ballot(ok);
+        __builtin_amdgcn_wave_barrier();
+        if (!m) {
+            if (valid) L.tab[h] = uint16_t(p + 1);
+            cursor += 64 * stride;
+            continue;
+        }
+        const uint32_t f = uint32_t(__ffsll((unsigned long long)m) - 1);
+        uint32_t q = cursor + f * stride;
+        uint32_t cq = uint32_t(__builtin_amdgcn_readlane(int(c), int(f)));
+        uint32_t len = 4;
+        // backwards over what the stride skipped: the destination not past the
+        // last match's end, the source not past the window's start (the
+        // distance stays what the compare allowed)
+        for (;;) {
+            const uint32_t room = min(q - anchor, cq);
+            if (!room) break;
+            const uint32_t k = lane + 1;
+            const bool eq = k <= room && wide_rd8(L.data, q - k) == wide_rd8(L.data, cq - k);
+            const uint64_t mm = __ballot(!eq);
+            const uint32_t run = mm ? uint32_t(__ffsll((unsigned long long)mm) - 1) : 64u;
+            const uint32_t back = min(run, room);
+            q -= back;
+            cq -= back;
+            len += back;
+            if (back < 64) break;
+        }
+        for (;;) {  // forwards to end_lim at most (cq < q: the source stays in the window)
+            const uint32_t i = q + len + lane;
+            const bool eq = i < end_lim && wide_rd8(L.data, i) == wide_rd8(L.data, cq + len + lane);
+            const uint64_t mm = __ballot(!eq);
+            if (!mm) {
+                len += 64;
+                continue;
+            }
+            len += uint32_t(__ffsll((unsigned long long)mm) - 1);
+            break;
+        }
+        if (lane == 0) rec[nrec] = make_uint2((q - hist) | ((q - cq) << 16), len);
+        ++nrec;
+        if (valid && p < q + len) L.tab[h] = uint16_t(p + 1);
+        __builtin_amdgcn_wave_barrier();
+        anchor = cursor = q + len;
+    }
+    if (lane == 0) {
+        B.nrec[g] = nrec;
+        B.trail[g] = W - anchor;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 static cdc::AesTables g_tab;
@@ -1397,8 +1544,17 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                                  uint32_t n, int compress, const uint8_t *key, const uint8_t *random, uint8_t *d_out,
                                  uint64_t out_cap, uint64_t *out_offsets, void *stream)
 {
+    return cdc_encode_device_level(device, d_base, offsets, lens, n, compress, key, random, d_out, out_cap, out_offsets,
+                                   CDC_LEVEL_FAST, stream);
+}
+
+extern "C" int cdc_encode_device_level(int device, const void *d_base, const uint64_t *offsets, const uint64_t *lens,
+                                       uint32_t n, int compress, const uint8_t *key, const uint8_t *random,
+                                       uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets, int level, void *stream)
+{
     if ((n && (!d_base || !offsets || !lens || !out_offsets)) || (key && !random) || !d_out) return CDC_E_INVALID;
     if (device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;
+    if (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE) return CDC_E_INVALID;
     // the selector: 0 none, 2 GZIP, every other value LZ4
     const int mode = compress == CDC_COMPRESS_GZIP ? 2 : compress ? 1 : 0;
     const bool gzip = mode == 2;
@@ -1493,6 +1649,7 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
                     S.src = K.src + uint64_t(g) * kSegLZ;
                     S.len = std::min<uint32_t>(kSegLZ, K.len - g * kSegLZ);
                     S.rem = K.len - g * kSegLZ;
+                    S.hist = seg_hist(level, g * kSegLZ);
                     segs[kg++] = S;
                 }
                 blks[kb++] = K;
@@ -1561,13 +1718,13 @@ extern "C" int cdc_encode_device(int device, const void *d_base, const uint64_t 
         ok = ok && hipMemcpyAsync(ws + o_xx, hp + h_xx, nb * 4, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok && n) {
         if (gzip) {
-            if (ng) hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+            launch_seq(Bt, level, ng, s);
             if (nsp) hipLaunchKernelGGL(k_dfl_size, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
         } else if (compress) {
             ok = hipEventRecord(C.fork, s) == hipSuccess && hipStreamWaitEvent(C.aux, C.fork, 0) == hipSuccess;
             hipLaunchKernelGGL(k_xxh32, dim3(xx_wgs), dim3(kXxWaves * 64), 0, C.aux, Bt);
             ok = ok && hipEventRecord(C.join, C.aux) == hipSuccess;
-            if (ng) hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+            launch_seq(Bt, level, ng, s);
             if (nk) hipLaunchKernelGGL(k_lz4_size, dim3(uint32_t(nk)), dim3(kBlkThreads), 0, s, Bt);
         }
         hipLaunchKernelGGL(k_enc_plan, dim3(1), dim3(kPlanThreads), 0, s, Bt);
@@ -1621,6 +1778,7 @@ extern "C" uint64_t cdc_encode_bound(uint64_t len, int compress, int encrypt)
 struct cdc_gzip_stream {
     int device = 0;
     bool first = true, closed = false;
+    int level = CDC_LEVEL_FAST;  // cdc_gzip_stream_set_level, before the first piece
     uint32_t reg = 0xFFFFFFFFu;  // CRC-32 register over the bytes so far
     uint64_t total = 0;
     std::mutex mu;
@@ -1646,6 +1804,15 @@ extern "C" void cdc_gzip_stream_free(cdc_gzip_stream *s)
 }
 
 extern "C" uint64_t cdc_gzip_stream_bound(uint64_t len) { return dfl::stream_piece_bound(len); }
+
+extern "C" int cdc_gzip_stream_set_level(cdc_gzip_stream *S, int level)
+{
+    if (!S || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(S->mu);
+    if (!S->first || S->closed) return CDC_E_INVALID;  // a member is written at one level
+    S->level = level;
+    return CDC_OK;
+}
 
 extern "C" int cdc_gzip_stream_piece(cdc_gzip_stream *S, const void *d_in, uint64_t len, int last, uint8_t *d_out,
                                      uint64_t out_cap, uint64_t *out_len, void *stream)
@@ -1729,6 +1896,7 @@ extern "C" int cdc_gzip_stream_piece(cdc_gzip_stream *S, const void *d_in, uint6
                 G.src = src + uint64_t(g) * kSegLZ;
                 G.len = std::min<uint32_t>(kSegLZ, blen - g * kSegLZ);
                 G.rem = blen - g * kSegLZ;
+                G.hist = seg_hist(S->level, g * kSegLZ);
                 segs[kg + g] = G;
             }
             kg += nseg;
@@ -1769,7 +1937,7 @@ extern "C" int cdc_gzip_stream_piece(cdc_gzip_stream *S, const void *d_in, uint6
     uint64_t back[4] = {0, 0, 0, 0};  // status[0..1], res[0..1]: consecutive 16-byte regions
     bool ok = o_res == o_status + 16 && hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+        launch_seq(Bt, S->level, ng, s);
         hipLaunchKernelGGL(k_dfl_size, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
         hipLaunchKernelGGL(k_gzs_plan, dim3(1), dim3(64), 0, s, Bt, A);
         hipLaunchKernelGGL(k_dfl_emit, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);

@@ -22,9 +22,17 @@ constexpr uint32_t kRecCap = kSegLZ / 4 + 2;  // records per segment (a match pe
 
 struct Seg {             // an 8-KiB LZ4 search segment
     uint64_t src;        // byte offset in the input base
-    uint32_t len;
+    uint16_t len;
+    uint16_t hist;       // bytes before it a match may copy from: 0 at CDC_LEVEL_FAST, at CDC_LEVEL_WIDE
+                         // min(kWideHist, its offset in its LZ4 block): never before the block, blob or piece
     uint32_t rem;        // bytes from the segment's start to its LZ4 block's end
 };
+static_assert(sizeof(Seg) == 16 && kSegLZ <= 0xFFFFu, "len and hist share the word len alone had");
+
+constexpr uint32_t kWideHist = 32768;  // CDC_LEVEL_WIDE's window before a segment (DEFLATE's; half of LZ4's reach)
+
+// A segment's hist at `level`: seg_off is its offset in its 4-MiB block.
+inline uint16_t seg_hist(int level, uint32_t seg_off) { return level ? uint16_t(seg_off < kWideHist ? seg_off : kWideHist) : uint16_t(0); }
 
 struct Blk {             // a 4-MiB LZ4 block
     uint64_t src;
@@ -102,7 +110,16 @@ static_assert(kDflThreads == 256 && dfl::kSeg == kSegLZ && kBlockLZ % dfl::kSpan
 // Defined in cdc_encode.hip; another translation unit launches them through
 // their host stubs (the device code stays in cdc_encode.hip's code object).
 __global__ __launch_bounds__(kSeqWaves * 64) void k_lz4_seq(const Batch B);
+__global__ __launch_bounds__(64) void k_lz_seq_wide(const Batch B);  // a wave per segment and workgroup
 __global__ __launch_bounds__(kDflThreads) void k_dfl_size(const Batch B);
 __global__ __launch_bounds__(kDflThreads) void k_dfl_emit(const Batch B);
+
+// The match search of a batch's ng segments at `level` (the plan filled Seg.hist with seg_hist at the same level).
+inline void launch_seq(const Batch &Bt, int level, size_t ng, hipStream_t s)
+{
+    if (!ng) return;
+    if (level) hipLaunchKernelGGL(k_lz_seq_wide, dim3(uint32_t(ng)), dim3(64), 0, s, Bt);
+    else hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+}
 
 }  // namespace enc

@@ -3,6 +3,8 @@
 //
 // Kernels, in launch order (one call = n pieces of one device buffer):
 //   k_lz4_seq     cdc_encode.hip's, unchanged: the match search per 8-KiB segment
+//                 (k_lz_seq_wide at CDC_LEVEL_WIDE: a piece's segments may copy
+//                 from up to 32 KiB before them inside the piece)
 //   k_dfl_size    cdc_encode.hip's, unchanged: per 32-KiB span its size as fixed
 //                 and as dynamic Huffman, the dynamic header, its CRC-32
 //   k_zip_plan    one wave per piece: each span's form at its bit from bit 0,
@@ -222,6 +224,16 @@ extern "C" int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src
                                      const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out, uint64_t out_cap,
                                      cdc_zip_piece_out *outs, uint64_t *total, void *stream)
 {
+    return cdc_zip_pieces_device_level(device, d_src, src_cap, pieces, n, hdr_arena, hdr_arena_len, d_out, out_cap, outs,
+                                       total, CDC_LEVEL_FAST, stream);
+}
+
+extern "C" int cdc_zip_pieces_device_level(int device, const void *d_src, uint64_t src_cap, const cdc_zip_piece *pieces,
+                                           uint32_t n, const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out,
+                                           uint64_t out_cap, cdc_zip_piece_out *outs, uint64_t *total, int level,
+                                           void *stream)
+{
+    if (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE) return CDC_E_INVALID;
     if (!total || (n && (!pieces || !outs))) return CDC_E_INVALID;
     *total = 0;
     if (device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;
@@ -292,6 +304,7 @@ extern "C" int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src
                     G.src = src + uint64_t(g) * kSegLZ;
                     G.len = std::min<uint32_t>(kSegLZ, blen - g * kSegLZ);
                     G.rem = blen - g * kSegLZ;
+                    G.hist = seg_hist(level, g * kSegLZ);
                     segs[kg + g] = G;
                 }
                 kg += nseg;
@@ -330,7 +343,7 @@ extern "C" int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src
     uint64_t back[4] = {0, 0, 0, 0};  // status[0..1], tot[0..1]: consecutive 16-byte regions
     bool ok = o_tot == o_status + 16 && hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok) {
-        if (ng) hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
+        launch_seq(Bt, level, ng, s);
         if (nsp) hipLaunchKernelGGL(k_dfl_size, dim3(uint32_t(nsp)), dim3(kDflThreads), 0, s, Bt);
         hipLaunchKernelGGL(k_zip_plan, dim3(n), dim3(64), 0, s, Bt, A);
         hipLaunchKernelGGL(k_zip_place, dim3(1), dim3(kZipPlaceThreads), 0, s, Bt, A);

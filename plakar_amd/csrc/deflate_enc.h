@@ -5,11 +5,13 @@
 // and undefined-behaviour sanitizers) against zlib.
 //
 // A blob is cut into spans of kSpanSegs match-search segments (32 KiB).  The
-// match search's records (k_lz4_seq: match start, offset, length, segment-
-// relative, sorted, not overlapping, length >= 4, offset < 8 KiB) are the input;
-// what lies between the matches is literals.  A span becomes one block: stored,
-// fixed Huffman or dynamic Huffman, whichever is smallest by exact bit count
-// at the bit position where it starts (choose_block).
+// match search's records (k_lz4_seq or k_lz_seq_wide: match start, offset,
+// length, segment-relative, sorted, not overlapping, length >= 4; the offset
+// reaches at most the segment's `hist` bytes before it, 0 for k_lz4_seq, and
+// never past 32,768) are the input; what lies between the matches is
+// literals.  A span becomes one block: stored, fixed Huffman or dynamic
+// Huffman, whichever is smallest by exact bit count at the bit position where
+// it starts (choose_block).
 //
 // The work inside a span is shared by "stretches" of kStretch bytes: a lane owns
 // the symbols that start inside its stretch (the literals there and every piece
@@ -43,6 +45,7 @@ constexpr uint32_t kLitSlots = 288, kDistSlots = 32;
 constexpr uint32_t kMaxTok = kNLit + kNDist;     // code lengths in a dynamic header, and its tokens at most
 constexpr uint32_t kHdrWords = 96;               // >= (14 + 57 + 7 * kMaxTok) bits: see write_header
 constexpr uint32_t kStored = 0, kFixed = 1, kDynamic = 2;
+constexpr uint32_t kMaxDist = 32768;             // DEFLATE's window, and the wide match search's
 constexpr uint64_t kMaxBlob = 0x7FFFFFFFull;     // ISIZE is 32 bits and Decode refuses 2 GiB or more
 
 struct Rec {                                     // uint2 on the device
@@ -110,13 +113,24 @@ DFL_HD uint32_t split_piece(uint32_t L, uint32_t k)
 }
 
 // ---- the walk -------------------------------------------------------------------------
+// Whether a record is written as a match.  The match search writes no offset
+// of 0, none that reaches further than hist bytes before the segment or past
+// DEFLATE's 32,768, and no length under 4: such a record's bytes are literals,
+// in the range where it starts and in the ranges it reaches into.
+DFL_HD bool rec_taken(const Rec &r, uint32_t hist)
+{
+    const uint32_t off = r.x >> 16;
+    return off - 1u < (r.x & 0xFFFFu) + hist && off <= kMaxDist && r.y >= 4;
+}
+
 // The symbols that start in [p0, p1) of a segment, in order: f.lit(p) for a
 // literal at p, f.match(offset, length) for a record that starts there.  A
 // record that reaches into the range from before it covers the range's first
 // bytes.  A record that starts before the walk's position (none is written by
-// the match search) is passed over, its bytes literals.
+// the match search) is passed over, its bytes literals.  hist: the bytes in
+// front of the segment that a record's offset may reach (SpanView).
 template <class F>
-DFL_HD void walk(const Rec *rec, uint32_t nrec, uint32_t p0, uint32_t p1, F &f)
+DFL_HD void walk(const Rec *rec, uint32_t nrec, uint32_t hist, uint32_t p0, uint32_t p1, F &f)
 {
     uint32_t lo = 0, hi = nrec;  // the first record that starts at or after p0
     while (lo < hi) {
@@ -125,15 +139,13 @@ DFL_HD void walk(const Rec *rec, uint32_t nrec, uint32_t p0, uint32_t p1, F &f)
         else hi = mid;
     }
     uint32_t i = lo, p = p0;
-    if (i > 0) {
+    if (i > 0 && rec_taken(rec[i - 1], hist)) {
         const uint32_t e = (rec[i - 1].x & 0xFFFFu) + rec[i - 1].y;
         if (e > p) p = e;
     }
     while (p < p1) {
         while (i < nrec && (rec[i].x & 0xFFFFu) < p) ++i;
-        // (nor does it write an offset of 0 or one that reaches before the
-        // segment, or a length under 4: such a record's bytes are literals too)
-        if (i < nrec && (rec[i].x & 0xFFFFu) == p && (rec[i].x >> 16) - 1u < p && rec[i].y >= 4) {
+        if (i < nrec && (rec[i].x & 0xFFFFu) == p && rec_taken(rec[i], hist)) {
             const Rec r = rec[i++];
             f.match(r.x >> 16, r.y);
             p += r.y;
@@ -150,6 +162,7 @@ struct SpanView {
     const Rec *rec[kSpanSegs];
     uint32_t nrec[kSpanSegs];
     uint32_t len;
+    uint32_t hist[kSpanSegs];  // bytes before each segment that its records may copy from (0: none)
 };
 
 // Stretch t of the span: its segment and range there; false past the span's end.
@@ -198,7 +211,7 @@ DFL_HD void span_hist(Par &par, const SpanView &V, Rd &rd, uint32_t *lfreq, uint
         uint32_t seg, p0, p1;
         if (!stretch_range(V, t, seg, p0, p1)) break;
         HistF<Par, Rd> f{par, rd, seg * kSeg, lfreq, dfreq, 0};
-        walk(V.rec[seg], V.nrec[seg], p0, p1, f);
+        walk(V.rec[seg], V.nrec[seg], V.hist[seg], p0, p1, f);
         if (f.xbits) par.add(xbits, f.xbits);
     }
     if (par.lane == 0) par.add(&lfreq[kEob], 1u);
@@ -602,7 +615,7 @@ DFL_HD void span_count(Par &par, const SpanView &V, Rd &rd, const Codes &C, uint
         uint32_t seg, p0, p1, bits = 0;
         if (stretch_range(V, t, seg, p0, p1)) {
             CountWalk<Rd> f{C, rd, seg * kSeg, 0};
-            walk(V.rec[seg], V.nrec[seg], p0, p1, f);
+            walk(V.rec[seg], V.nrec[seg], V.hist[seg], p0, p1, f);
             bits = f.bits;
         }
         sbits[t] = bits;
@@ -643,7 +656,7 @@ DFL_HD uint64_t span_pack(Par &par, const SpanView &V, Rd &rd, const Codes &C, c
         for (uint32_t u = 0; u < t; ++u) off += sbits[u];
         BitW<Par> B(par, words, s0 + off);
         PackWalk<Par, Rd> f{C, rd, seg * kSeg, B};
-        walk(V.rec[seg], V.nrec[seg], p0, p1, f);
+        walk(V.rec[seg], V.nrec[seg], V.hist[seg], p0, p1, f);
         B.flush();
     }
     if (par.lane == 0) {

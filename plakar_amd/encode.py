@@ -3,7 +3,9 @@
 (compression/compression.go:94-106) or the gzip member of DeflateGzipStream
 (compression.go:78-92), then the AES-256-GCM stream of
 encryption.EncryptStream (encryption/symmetric.go:72-163) when a key is
-configured.  Every call goes through the C ABI (cdc_encode_device)."""
+configured.  Every call goes through the C ABI (cdc_encode_device, or
+cdc_encode_device_level for `level=1`: a match search with a 32-KiB window
+before each 8-KiB segment, smaller output, the same formats)."""
 import ctypes
 import os
 
@@ -159,13 +161,15 @@ def encode_bound(n, compress=True, encrypt=True):
     return int(lib().cdc_encode_bound(int(n), _sel(compress), int(bool(encrypt))))
 
 
-def encode_device(base, offsets, lens, out, key=None, compress=True, random=None, device=0, stream=None):
+def encode_device(base, offsets, lens, out, key=None, compress=True, random=None, device=0, stream=None, level=0):
     """Encode blobs that live in the device tensor `base` (uint8) at the given
     byte offsets/lengths (sequences or numpy arrays) into the device tensor
     `out`; returns the n + 1 output offsets (int64 numpy array).  `compress`:
-    False, True (an LZ4 frame) or "GZIP" (a gzip member)."""
+    False, True (an LZ4 frame) or "GZIP" (a gzip member).  `level`: 0 (matches
+    inside 8-KiB segments) or 1 (from up to 32 KiB before the segment)."""
     import torch
     sel = _sel(compress)
+    level = _lib.level_code(level)
     ensure_init()
     n = len(lens)
     u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -186,15 +190,18 @@ def encode_device(base, offsets, lens, out, key=None, compress=True, random=None
         else:
             random = bytes(random)
     st = stream if stream is not None else torch.cuda.current_stream(device)
-    check(lib().cdc_encode_device(int(device), ctypes.c_void_p(base.data_ptr()), offs, lns, n, sel,
-                                  key, random if key is not None else None, ctypes.c_void_p(out.data_ptr()),
-                                  out.numel(), oo, ctypes.c_void_p(st.cuda_stream)), "cdc_encode_device")
+    args = (int(device), ctypes.c_void_p(base.data_ptr()), offs, lns, n, sel, key, random if key is not None else None,
+            ctypes.c_void_p(out.data_ptr()), out.numel(), oo)
+    if level:
+        check(lib().cdc_encode_device_level(*args, level, ctypes.c_void_p(st.cuda_stream)), "cdc_encode_device_level")
+    else:
+        check(lib().cdc_encode_device(*args, ctypes.c_void_p(st.cuda_stream)), "cdc_encode_device")
     return oo_a.astype(np.int64)
 
 
-def encode_blobs(blobs, key=None, compress=True, random=None, device=0):
+def encode_blobs(blobs, key=None, compress=True, random=None, device=0, level=0):
     """Encode host byte buffers (numpy uint8 arrays or bytes): a list of the
-    encoded bytes, blob by blob.  `compress` as for encode_device."""
+    encoded bytes, blob by blob.  `compress` and `level` as for encode_device."""
     import torch
     arrs = [np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray)) else np.asarray(b, np.uint8).ravel()
             for b in blobs]
@@ -206,7 +213,8 @@ def encode_blobs(blobs, key=None, compress=True, random=None, device=0):
         base[:int(offs[-1])].copy_(torch.from_numpy(np.concatenate(arrs)))
     cap = sum(encode_bound(n, compress, key is not None) for n in lens)
     out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-    oo = encode_device(base, offs[:-1], lens, out, key=key, compress=compress, random=random, device=device)
+    oo = encode_device(base, offs[:-1], lens, out, key=key, compress=compress, random=random, device=device,
+                       level=level)
     host = out[:int(oo[-1])].cpu().numpy()
     return [host[oo[i]:oo[i + 1]].tobytes() for i in range(len(lens))]
 
@@ -215,16 +223,18 @@ class DeviceEncoder:
     """(*Repository).Encode with the repository's configuration: compression
     "LZ4" (compression.DefaultConfiguration), "GZIP" or None, and the encryption key
     (None: no encryption).  `encode_many` encodes a whole batch of blobs in
-    one device call; calling the object encodes one blob, like Encode."""
+    one device call; calling the object encodes one blob, like Encode.
+    `level`: compression.Configuration's Level as encode_device takes it."""
 
-    def __init__(self, key=None, compression="LZ4", device=0):
+    def __init__(self, key=None, compression="LZ4", device=0, level=0):
         code = _lib.compress_code(compression)  # ValueError for any other name
+        self.level = _lib.level_code(level)
         self.key = None if key is None else bytes(key)
         self.compress = "GZIP" if code == _lib.CDC_COMPRESS_GZIP else bool(code)
         self.device = device
 
     def encode_many(self, blobs):
-        return encode_blobs(blobs, key=self.key, compress=self.compress, device=self.device)
+        return encode_blobs(blobs, key=self.key, compress=self.compress, device=self.device, level=self.level)
 
     def __call__(self, blob):
         return self.encode_many([blob])[0]

@@ -303,12 +303,14 @@ class BackupSession:
     run() is one backup of a list of files through the pipeline of
     cdc_backup_files (reads + object SHA-256, cut points, chunk SHA-256 +
     histograms, dedup, Encode, `packers` concurrent packerJob workers,
-    snapshot/snapshot.go:51-92)."""
+    snapshot/snapshot.go:51-92).  `level`: Encode's match search in this
+    session's runs (0, or 1: a 32-KiB window, smaller blobs; cdc_backup_set_level)."""
 
     def __init__(self, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
-                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0):
+                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, level=0):
         import ctypes
         from . import _lib, packer as packer_mod
+        level = _lib.level_code(level)  # ValueError for any value but 0 and 1
         repo = repo or Repository()
         cfg = repo.Chunking
         opts = chunkers.ChunkerOpts(MinSize=int(cfg.MinSize), NormalSize=int(cfg.NormalSize),
@@ -334,6 +336,8 @@ class BackupSession:
             o.known, o.nknown = ctypes.cast(knownbuf, ctypes.c_void_p), len(ks)
         self._h = ctypes.c_void_p()
         _lib.check(_lib.lib().cdc_backup_new(int(dev), ctypes.byref(o), ctypes.byref(self._h)), "cdc_backup_new")
+        if level:
+            _lib.check(_lib.lib().cdc_backup_set_level(self._h, level), "cdc_backup_set_level")
 
     def run(self, paths, keep_packfiles=True, content_type=None):
         """Back up the files: (objects, packfiles, stats), as backup_files.
@@ -430,7 +434,7 @@ class BackupSession:
 
 
 def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
-                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, keep_packfiles=True):
+                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, keep_packfiles=True, level=0):
     """One backup of a list of files through the native pipeline (a
     BackupSession for this call only).  known: iterable of 32-byte digests
     already in the repository (not stored again).  Returns (objects,
@@ -439,7 +443,7 @@ def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", kn
     does), the serialised packfiles in the order the packers flushed them,
     and the per-stage stats of cdc_backup_stats."""
     with BackupSession(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp,
-                       dev) as s:
+                       dev, level) as s:
         return s.run(paths, keep_packfiles)
 
 

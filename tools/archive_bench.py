@@ -21,7 +21,11 @@ thread of zipfile.ZipFile(..., ZIP_DEFLATED, compresslevel=6) over the same
 files (the reference's shape: one compress/flate writer over every file in
 turn) with its size, and the deflate stage against a loop of one
 GzipStream piece per entry over the same bytes on the device (five launches, a
-readback and a synchronise per entry), timed once."""
+readback and a synchronise per entry), timed once.
+
+--level 1: tar.gz and zip are written with the wide match search
+(cdc_archive_set_level), and level 0 runs beside it in the same process: its
+GiB/s and archive size are the *_l0_* figures."""
 import argparse
 import json
 import os
@@ -66,20 +70,26 @@ def zip_sets(a):
                 paths.append(p)
             objs, packs, _ = snapshot.backup_files(paths, key=key)
             ents = [archive.ArchiveEntry(f"set/{os.path.basename(p)}", o, mtime=1_700_000_000) for p, o in zip(paths, objs)]
-            line = dict(set=name, reps=a.reps, files=len(paths), file_bytes=int(data.size))
+            line = dict(set=name, reps=a.reps, files=len(paths), file_bytes=int(data.size), level=a.level)
             for fmt in ("zip", "tarball"):
                 out = os.path.join(work, "out.zip" if fmt == "zip" else "out.tar.gz")
-                best = None
-                with (archive.ZipSession(key=key) if fmt == "zip" else archive.ArchiveSession(key=key, format=fmt)) as s:
-                    for p in packs:
-                        s.add_packfile(p)
-                    for _ in range(a.reps + 1):  # the first run grows the buffers
-                        _, statuses, st = s.run(ents, path=out)
-                        assert not any(statuses)
-                        if best is None or st["wall_s"] < best["wall_s"]:
-                            best = st
-                line[f"{fmt}_gibs"] = data.size / best["wall_s"] / 2**30
-                line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})
+                for lv in ((0, a.level) if a.level else (0,)):  # --level's run last: its file is the one read back
+                    best = None
+                    with (archive.ZipSession(key=key, level=lv) if fmt == "zip"
+                          else archive.ArchiveSession(key=key, format=fmt, level=lv)) as s:
+                        for p in packs:
+                            s.add_packfile(p)
+                        for _ in range(a.reps + 1):  # the first run grows the buffers
+                            _, statuses, st = s.run(ents, path=out)
+                            assert not any(statuses)
+                            if best is None or st["wall_s"] < best["wall_s"]:
+                                best = st
+                    if lv != a.level:  # level 0 beside --level 1: speed and size
+                        line.update({f"{fmt}_l0_gibs": data.size / best["wall_s"] / 2**30,
+                                     f"{fmt}_l0_output_bytes": best["output_bytes"]})
+                        continue
+                    line[f"{fmt}_gibs"] = data.size / best["wall_s"] / 2**30
+                    line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})
             with zipfile.ZipFile(os.path.join(work, "out.zip")) as z:
                 ok = z.testzip() is None and len(z.namelist()) == len(paths)
                 for i in sorted({0, len(paths) // 2, len(paths) - 1}):
@@ -127,6 +137,8 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--tmp", default=None, help="directory for the files (default: a temporary one)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--level", type=int, default=0, choices=(0, 1),
+                    help="the match search of tar.gz and zip (1: a 32-KiB window); level 0 is then run beside it (*_l0_*)")
     a = ap.parse_args()
     if a.format == "zip":
         return zip_sets(a)
@@ -156,21 +168,26 @@ def main():
                 paths.append(p)
             objs, packs, _ = snapshot.backup_files(paths, key=key)
             ents = [archive.ArchiveEntry(f"set/{os.path.basename(p)}", o, mtime=1_700_000_000) for p, o in zip(paths, objs)]
-            line = dict(set=name, reps=a.reps, files=len(paths))
+            line = dict(set=name, reps=a.reps, files=len(paths), level=a.level)
             tar_path = os.path.join(work, "out.tar")
             for fmt in ("tar", "tarball"):
                 out = tar_path if fmt == "tar" else os.path.join(work, "out.tar.gz")
-                best = None
-                with archive.ArchiveSession(key=key, format=fmt) as s:
-                    for p in packs:
-                        s.add_packfile(p)
-                    for _ in range(a.reps + 1):  # the first run grows the buffers
-                        _, statuses, st = s.run(ents, path=out)
-                        assert not any(statuses)
-                        if best is None or st["wall_s"] < best["wall_s"]:
-                            best = st
-                line[f"{fmt}_gibs"] = best["stream_bytes"] / best["wall_s"] / 2**30
-                line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})
+                for lv in ((0, a.level) if a.level and fmt == "tarball" else (a.level,)):  # --level's run last
+                    best = None
+                    with archive.ArchiveSession(key=key, format=fmt, level=lv) as s:
+                        for p in packs:
+                            s.add_packfile(p)
+                        for _ in range(a.reps + 1):  # the first run grows the buffers
+                            _, statuses, st = s.run(ents, path=out)
+                            assert not any(statuses)
+                            if best is None or st["wall_s"] < best["wall_s"]:
+                                best = st
+                    if lv != a.level:  # level 0 beside --level 1: speed and size
+                        line.update({f"{fmt}_l0_gibs": best["stream_bytes"] / best["wall_s"] / 2**30,
+                                     f"{fmt}_l0_output_bytes": best["output_bytes"]})
+                        continue
+                    line[f"{fmt}_gibs"] = best["stream_bytes"] / best["wall_s"] / 2**30
+                    line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})
             with open(tar_path, "rb") as f:
                 tar = f.read()
             with open(os.path.join(work, "out.tar.gz"), "rb") as f:

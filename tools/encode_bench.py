@@ -11,6 +11,11 @@ One JSON line per set:
 
     python tools/encode_bench.py --gzip [--sets c1,c3,text] [--size-mib 128] [--reps 3]
 
+With --level 1 every label runs at both levels in the same process (level 1:
+the match search with a 32-KiB window, k_lz_seq_wide): the level-1 figures
+carry the suffix _l1, the round trip is checked at both levels, and liblz4's
+block size of the same chunks stands beside zlib's.
+
 Per-kernel times come from a kernel trace of the same command
 (rocprofv3 --kernel-trace --stats -- python tools/encode_bench.py --gzip ...).
 """
@@ -53,6 +58,7 @@ def gzip_sets(a):
             best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
         return r, best / 1e3
 
+    levels = (0, 1) if a.level else (0,)
     for name in a.sets.split(","):
         if name == "text":
             buf = torch.from_numpy(np.frombuffer(decode_bench.text_like(np, size), dtype=np.uint8).copy()).to(dev)
@@ -72,16 +78,18 @@ def gzip_sets(a):
                 continue
             cap = sum(encode.encode_bound(int(x), comp, k is not None) for x in lens)
             enc = torch.empty(cap, dtype=torch.uint8, device=dev)
-            oo, enc_s = timed(lambda: encode.encode_device(buf, offs, lens, enc, key=k, compress=comp))
-            tag = label.replace("+", "_")
-            line.update({f"{tag}_s": enc_s, f"{tag}_gibs": n / enc_s / 2**30, f"{tag}_bytes": int(oo[-1])})
-            if label == "gzip+gcm":  # the round trip, on the device
-                out = torch.empty(n, dtype=torch.uint8, device=dev)
-                doo, st = decode.decode_device(enc, oo[:-1], np.diff(oo), out, key=k, compressed="GZIP")
-                line["round_trip_ok"] = bool((st == 0).all()) and int(doo[-1]) == n and all(
-                    torch.equal(out[int(doo[i]):int(doo[i + 1])], buf[int(offs[i]):int(offs[i]) + int(lens[i])])
-                    for i in range(len(lens)))
-                del out
+            for lv in levels:
+                oo, enc_s = timed(lambda: encode.encode_device(buf, offs, lens, enc, key=k, compress=comp, level=lv))
+                tag = label.replace("+", "_") + ("_l1" if lv else "")
+                line.update({f"{tag}_s": enc_s, f"{tag}_gibs": n / enc_s / 2**30, f"{tag}_bytes": int(oo[-1])})
+                if label in ("gzip+gcm", "lz4+gcm") and (lv or label == "gzip+gcm"):  # the round trip, on the device
+                    out = torch.empty(n, dtype=torch.uint8, device=dev)
+                    doo, st = decode.decode_device(enc, oo[:-1], np.diff(oo), out, key=k, compressed=comp)
+                    ok = bool((st == 0).all()) and int(doo[-1]) == n and all(
+                        torch.equal(out[int(doo[i]):int(doo[i + 1])], buf[int(offs[i]):int(offs[i]) + int(lens[i])])
+                        for i in range(len(lens)))
+                    line["round_trip_ok" if label == "gzip+gcm" and not lv else f"{tag}_round_trip_ok"] = ok
+                    del out
             del enc
         if not a.no_host:
             host = buf.cpu().numpy()
@@ -95,6 +103,13 @@ def gzip_sets(a):
                         host_zlib6_bytes=zbytes + 12 * len(lens))
             if "gzip_s" in line:
                 line["device_over_host"] = host_s / line["gzip_s"]
+            if a.level:
+                import lz4_ref
+                with ThreadPoolExecutor(a.host_threads) as pool:
+                    # a chunk is at most one 4-MiB block: the block, and the frame's 19 bytes around it
+                    line["host_liblz4_bytes"] = sum(pool.map(lz4_ref.lz4_block_size, plains)) + 19 * len(lens)
+                if "gzip_gcm_l1_s" in line:
+                    line["level1_gzip_gcm_over_host"] = host_s / line["gzip_gcm_l1_s"]
         print(json.dumps(line), flush=True)
         del buf
 
@@ -109,6 +124,7 @@ def main():
     ap.add_argument("--sets", default="c1,c3,text")
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--level", type=int, default=0, choices=(0, 1), help="1: every label at both levels, level 1 as *_l1")
     a = ap.parse_args()
     if a.gzip:
         a.reps = a.reps or 3
@@ -144,15 +160,16 @@ def main():
                 continue
             cap = sum(encode.encode_bound(x, comp, k is not None) for x in lens)
             out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            encode.encode_device(t, offs, lens, out, key=k, compress=comp)  # warm
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(a.reps):
-                oo = encode.encode_device(t, offs, lens, out, key=k, compress=comp)
-            torch.cuda.synchronize()
-            el = (time.perf_counter() - t0) / a.reps
-            print(f"{kind:12s} {label:8s} {len(lens):6d} blobs  {n / el / 2**30:8.1f} GiB/s  ratio {oo[-1] / n:.3f}",
-                  flush=True)
+            for lv in ((0, 1) if a.level and comp else (0,)):
+                encode.encode_device(t, offs, lens, out, key=k, compress=comp, level=lv)  # warm
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.reps):
+                    oo = encode.encode_device(t, offs, lens, out, key=k, compress=comp, level=lv)
+                torch.cuda.synchronize()
+                el = (time.perf_counter() - t0) / a.reps
+                print(f"{kind:12s} {label:8s} level {lv} {len(lens):6d} blobs  {n / el / 2**30:8.1f} GiB/s  "
+                      f"ratio {oo[-1] / n:.3f}", flush=True)
 
 
 if __name__ == "__main__":
