@@ -3,7 +3,8 @@
 (tests/c/wide_records_check.cpp under the sanitizers, each member judged by
 zlib there and walked by inflate_ref here), the new entry points' argument
 checks before the device, the Python keywords, the exported symbols and the
-compiler's resource report of k_lz_seq_wide."""
+compiler's resource report of k_lz_seq_wide, and the generator of contents
+with planted repeats (tests/planted.py) that the device tests feed it."""
 import ctypes
 import inspect
 import os
@@ -15,6 +16,7 @@ import zlib
 import pytest
 
 import inflate_ref as ir
+import planted
 from plakar_amd import _lib, archive, build, encode, snapshot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -241,3 +243,55 @@ def test_wide_kernel_resources():
     assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0
     assert int(k["ScratchSize [bytes/lane]"]) < PRIVATE_MAX
     assert 40960 + 2 * 8192 <= int(k["LDS Size [bytes/block]"]) <= LDS_MAX, "the window and a table of at least 8,192 u16"
+
+
+# ---- the planted generator (tests/planted.py) that tests/test_encode_wide_planted.py feeds the device ----
+def test_planted_is_deterministic_and_replays():
+    for mode in ("free", "edges", "far"):
+        for n, seed in ((0, 1), (1, 2), (5, 3), (8193, 4), (70_001, 5), (300_000, 6)):
+            content, plants = planted.planted(n, seed, mode)
+            assert (content, plants) == planted.planted(n, seed, mode) and len(content) == n
+            assert planted.replay(content, plants) == content, (mode, n, seed)
+            assert all(1 <= d <= min(pos, planted.DIST_MAX) and 1 <= ln <= planted.RUN_MAX for pos, ln, d in plants)
+            assert all(a[0] + a[1] <= b[0] for a, b in zip(plants, plants[1:])), "ascending, no copy inside another"
+            if mode == "edges":
+                assert all(d in planted.EDGES or d == pos for pos, _, d in plants)
+            if mode == "far":
+                assert all(d > planted.FAR for _, _, d in plants)
+    assert planted.planted(70_001, 5)[0] != planted.planted(70_001, 6)[0]
+    with pytest.raises(ValueError):
+        planted.planted(10, 1, "near")
+
+
+def test_planted_has_what_the_search_is_to_meet():
+    content, plants = planted.planted(1 << 20, 11, "edges")
+    assert {d for _, _, d in plants} >= set(planted.EDGES)
+    assert any(d < ln for _, ln, d in plants), "a copy that overlaps itself"
+    content, plants = planted.planted(1 << 20, 12)
+    touching = sum(a[0] + a[1] == b[0] for a, b in zip(plants, plants[1:]))
+    literal_runs = len(plants) - touching + 1
+    assert 0.15 < touching / (len(plants) + literal_runs) < 0.35, "about one run in four is a copy right behind a copy"
+    lens = [ln for _, ln, _ in plants]
+    assert min(lens) <= 8 and max(lens) > 6000 and max(d for _, _, d in plants) > WINDOW
+    gaps = [b[0] - a[0] - a[1] for a, b in zip(plants, plants[1:])]
+    assert max(gaps) > SEG, "a repeat that begins deep inside a literal run of more than a segment"
+
+
+def test_planted_batches_reach_past_8192():
+    for content, plants in planted.window_blobs():
+        assert planted.replay(content, plants) == content
+        if len(content) > 2 * SEG:
+            assert planted.far_share(plants, len(content)) > 0
+    lens = [len(c) for c, _ in planted.window_blobs()]
+    assert {n // SEG for n in lens} == {1, 2, 3, 4, 5} and {n % SEG for n in lens} == set(planted.WINDOW_TAILS)
+    for _, n, seed, mode in planted.SIZE_CASES:
+        content, plants = planted.planted(n, seed, mode)
+        assert planted.far_share(plants, n) > 0.05
+    for seed in planted.BATCH_SEEDS:
+        batch = planted.seeded_batch(seed)
+        assert batch == planted.seeded_batch(seed) and 1 <= len(batch) <= 120
+        assert sum(len(c) >= planted.BLOCK for c, _ in batch) == 1
+        assert sum(planted.far_share(p, 1) for _, p in batch) > 0, seed
+    tile = planted.tile_blobs()
+    assert len(tile) == 1500 and all(9000 <= len(c) <= 20000 for c, _ in tile)
+    assert sum(planted.far_share(p, 1) for _, p in tile) > 0
