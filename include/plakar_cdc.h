@@ -188,12 +188,18 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
  *     its segment, never from before its 4-MiB block (LZ4's blocks stay
  *     independent; DEFLATE uses the same floor) nor from before its blob, piece
  *     or zip entry.  Smaller output, a slower search; the formats, the bounds
- *     and every reader are the same.
- * Every other value is CDC_E_INVALID; with CDC_COMPRESS_NONE the level changes
- * nothing.  cdc_transcode_device's re-encode and cdc_backup_run stay at
- * CDC_LEVEL_FAST. */
+ *     and every reader are the same;
+ *   CDC_LEVEL_BEST (9, gzip.BestCompression): the smallest the device writes.
+ *     CDC_LEVEL_WIDE's window and floors, with four earlier occurrences kept
+ *     per hash bucket, the longest of them taken, and a lazy look: a match
+ *     gives way to a strictly longer one that starts one byte later.  Slower
+ *     again; the formats, the bounds and every reader are the same.
+ * Every other value (2, 3, 6, -1, ...) is CDC_E_INVALID; with CDC_COMPRESS_NONE
+ * the level changes nothing.  cdc_transcode_device and cdc_backup_run are
+ * their _level forms at CDC_LEVEL_FAST. */
 #define CDC_LEVEL_FAST 0
 #define CDC_LEVEL_WIDE 1
+#define CDC_LEVEL_BEST 9
 
 /* cdc_encode_device at `level` (compression/compression.go:12-51): the level
  * changes which matches the LZ4 frame's sequences or the gzip member's blocks
@@ -440,6 +446,16 @@ int cdc_transcode_device(int device, const void *d_in, const uint64_t *offsets, 
                          const cdc_codec *src, const cdc_codec *dst, const uint8_t *checksums, const uint8_t *random,
                          uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets, int32_t *status, void *stream);
 
+/* cdc_transcode_device with the re-encode path's Encode at `level`
+ * (compression/compression.go:12-51; CDC_LEVEL_* above).  The re-key path, the
+ * paths that only open, seal or copy, and a destination without compression
+ * ignore it; a level that does not exist is CDC_E_INVALID on every path.
+ * cdc_transcode_device is this call with CDC_LEVEL_FAST. */
+int cdc_transcode_device_level(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                               const cdc_codec *src, const cdc_codec *dst, const uint8_t *checksums,
+                               const uint8_t *random, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
+                               int32_t *status, int level, void *stream);
+
 /* ---- packfile builder: the consumer of the cut lists ---------------------------
  * snapshot/packer.go + packfile/packfile.go: blobs are appended to a
  * packfile whose bytes are those of (*PackFile).Serialize (packfile.go:241-294):
@@ -583,11 +599,17 @@ void cdc_backup_free(cdc_backup *b);
 /* The level Encode runs at in later cdc_backup_files calls of this session
  * (compression/compression.go:12-51; CDC_LEVEL_* above): CDC_LEVEL_WIDE stores
  * smaller LZ4 or GZIP blobs.  A run in progress keeps the level it began with.
- * cdc_backup_run has no session and stays at CDC_LEVEL_FAST. */
+ * cdc_backup_run has no session: cdc_backup_run_level takes the level. */
 int cdc_backup_set_level(cdc_backup *b, int level);
 /* new + files + free in one call. */
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
                    cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats);
+/* cdc_backup_run with Encode at `level` (compression/compression.go:12-51;
+ * CDC_LEVEL_* above); a level that does not exist is CDC_E_INVALID before
+ * anything is opened.  cdc_backup_run is this call with CDC_LEVEL_FAST. */
+int cdc_backup_run_level(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
+                         cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats,
+                         int level);
 
 /* ---- restore: packfiles in, files out --------------------------------------------
  * The read path of snapshot/restore.go:103-110 (a reader per file handed to

@@ -5,6 +5,7 @@ the package.  If the shared library is missing, import fails loudly with the
 command that builds it.
 """
 import ctypes
+import numbers
 import os
 import sys
 import warnings
@@ -43,12 +44,23 @@ CDC_COMPRESS_GZIP = 2
 # match search Encode, the gzip stream, the zip pieces and the archive and backup sessions run
 CDC_LEVEL_FAST = 0  # matches inside their 8-KiB segment
 CDC_LEVEL_WIDE = 1  # matches from up to 32 KiB before the segment
+_LEVEL_BEST = 9     # CDC_LEVEL_BEST: the same window, four candidates per bucket and a lazy parse: the smallest
+
+
+def __getattr__(name):
+    # CDC_LEVEL_BEST is an attribute of the module without being in dir(): 9 is no
+    # status code, and a sweep over the module's CDC_* names (every status has a
+    # cdc_strerror text) takes each name's value for one.
+    if name == "CDC_LEVEL_BEST":
+        return _LEVEL_BEST
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def level_code(level):
-    """The C level for 0 / 1 (CDC_LEVEL_FAST / CDC_LEVEL_WIDE); ValueError otherwise."""
-    if isinstance(level, bool) or level not in (CDC_LEVEL_FAST, CDC_LEVEL_WIDE):
-        raise ValueError(f"unsupported level {level!r} (0: fast, 1: wide)")
+    """The C level for 0 / 1 / 9 (CDC_LEVEL_FAST / CDC_LEVEL_WIDE / CDC_LEVEL_BEST); ValueError otherwise."""
+    if (isinstance(level, bool) or not isinstance(level, numbers.Integral)
+            or level not in (CDC_LEVEL_FAST, CDC_LEVEL_WIDE, _LEVEL_BEST)):
+        raise ValueError(f"unsupported level {level!r} (0: fast, 1: wide, 9: best)")
     return int(level)
 
 
@@ -309,6 +321,11 @@ SIGNATURES = {
                                             ctypes.c_uint32, _P(cdc_codec), _P(cdc_codec), ctypes.c_char_p,
                                             ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
                                             _P(ctypes.c_int32), ctypes.c_void_p]),
+    "cdc_transcode_device_level": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64),
+                                                  _P(ctypes.c_uint64), ctypes.c_uint32, _P(cdc_codec), _P(cdc_codec),
+                                                  ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                  _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_int,
+                                                  ctypes.c_void_p]),
     "cdc_packfile_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, _P(cdc_packfile_footer),
                                           _P(cdc_packfile_row), ctypes.c_uint64, _P(ctypes.c_uint64)]),
     "cdc_assemble_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
@@ -336,6 +353,9 @@ SIGNATURES = {
     "cdc_set_maskl_index_mode": (ctypes.c_int, [ctypes.c_int]),
     "cdc_backup_run": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_char_p), ctypes.c_int, _P(cdc_backup_opts),
                                       BACKUP_FILE_FN, BACKUP_PACK_FN, ctypes.c_void_p, _P(cdc_backup_stats)]),
+    "cdc_backup_run_level": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_char_p), ctypes.c_int, _P(cdc_backup_opts),
+                                            BACKUP_FILE_FN, BACKUP_PACK_FN, ctypes.c_void_p, _P(cdc_backup_stats),
+                                            ctypes.c_int]),
     "cdc_backup_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_backup_opts), _P(ctypes.c_void_p)]),
     "cdc_backup_files": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_char_p), ctypes.c_int, BACKUP_FILE_FN,
                                         BACKUP_PACK_FN, ctypes.c_void_p, _P(cdc_backup_stats)]),

@@ -34,9 +34,10 @@ class GzipStream:
     concatenated, are what gzip.NewWriter(out) ... Close() gives for the
     concatenated inputs (any inflater reads them as one member).  Every
     piece ends on a byte boundary; the piece given with last=True closes the
-    member (CRC-32 of the whole stream, ISIZE mod 2^32).  `level`: 0, or 1
-    for matches from up to 32 KiB back inside a piece (set_level changes it
-    until the first piece is written)."""
+    member (CRC-32 of the whole stream, ISIZE mod 2^32).  `level`: 0, 1
+    for matches from up to 32 KiB back inside a piece, or 9 for the longest of
+    four candidates and a lazy parse as well (set_level changes it until the
+    first piece is written)."""
 
     def __init__(self, device=0, level=0):
         import torch  # noqa: F401  (torch's HIP runtime comes up before the library's)
@@ -128,7 +129,8 @@ class ArchiveSession:
     configuration (compression "LZ4", "GZIP" or None, the 32-byte key or
     None), the output format ("tar", or "tarball": tar.gz, the reference's
     default) and the registered packfiles.  `level`: the match search of the
-    tar.gz member (0, or 1: a 32-KiB window; cdc_archive_set_level)."""
+    tar.gz member (0; 1: a 32-KiB window; 9: and four candidates per bucket, a
+    lazy parse; cdc_archive_set_level)."""
 
     def __init__(self, key=None, compression="LZ4", format="tarball", verify=True, writers=8,
                  batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):

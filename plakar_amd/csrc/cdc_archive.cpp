@@ -607,7 +607,7 @@ int cdc_archive_new_zip(int device, const cdc_archive_opts *opts, cdc_archive **
 
 int cdc_archive_set_level(cdc_archive *a, int level)
 {
-    if (!a || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    if (!a || (!cdc::level_ok(level))) return CDC_E_INVALID;
     std::lock_guard<std::mutex> lk(a->run_mu);
     a->level = level;
     return CDC_OK;

@@ -1192,7 +1192,7 @@ int cdc_backup_new(int device, const cdc_backup_opts *opts, cdc_backup **out)
 
 int cdc_backup_set_level(cdc_backup *B, int level)
 {
-    if (!B || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    if (!B || !cdc::level_ok(level)) return CDC_E_INVALID;
     B->level.store(level);
     return CDC_OK;
 }
@@ -1367,9 +1367,18 @@ void cdc_backup_free(cdc_backup *b)
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
                    cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats)
 {
+    return cdc_backup_run_level(device, paths, n, opts, on_file, on_pack, ctx, stats, CDC_LEVEL_FAST);
+}
+
+int cdc_backup_run_level(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
+                         cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats,
+                         int level)
+{
+    if (!cdc::level_ok(level)) return CDC_E_INVALID;
     cdc_backup *b = nullptr;
     int st = cdc_backup_new(device, opts, &b);
     if (st != CDC_OK) return st;
+    (void)cdc_backup_set_level(b, level);
     st = cdc_backup_files(b, paths, n, on_file, on_pack, ctx, stats);
     cdc_backup_free(b);
     return st;

@@ -1506,6 +1506,215 @@ __global__ __launch_bounds__(64) void k_lz_seq_wide(const Batch B)
 }
 
 // ---------------------------------------------------------------------------
+// k_lz_seq_deep (CDC_LEVEL_BEST): k_lz_seq_wide's window, records and loop, with
+// a table of 4,096 buckets of four u16 window positions (the same 32 KiB: two
+// workgroups per CU) and a one-position lazy look.  A bucket is one 8-byte
+// word, the newest position in its low 16 bits; an insert shifts it by one way.
+// Lanes of one step that insert into one bucket lose each other's entries:
+// every candidate is verified, so any of them is sound.  A probe verifies all
+// four ways; the ways of the chosen position are measured side by side,
+// sixteen lanes and 64 bytes per way and turn, and the longest is taken, the
+// nearest among equals.  Before a match at q is taken, the best at q + 1 is
+// measured the same way, and again from there while it is strictly longer
+// (DESIGN.md 5.18).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDeepBucketBits = 12;
+constexpr uint32_t kDeepLazyMax = 128;  // a match this long is taken without the look (zlib's max_lazy)
+
+struct alignas(16) DeepLds {
+    uint32_t data[kWideWin / 4 + 4];          // the window and 16 zero bytes after it
+    uint64_t tab[1u << kDeepBucketBits];      // four ways of window position + 1 (0: empty), the newest lowest
+};
+static_assert(sizeof(DeepLds) <= 160u * 1024u && 2 * sizeof(DeepLds) <= 160u * 1024u, "two workgroups' LDS on a CU");
+static_assert(offsetof(DeepLds, tab) % 8 == 0, "a bucket is one 8-byte read");
+
+__device__ __forceinline__ uint32_t deep_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kDeepBucketBits); }
+
+struct DeepHit {
+    uint32_t len, c;  // the longest match of the ways at a position (0: none) and its source
+};
+
+// The four ways of `bucket` against position P, alike in every lane: way
+// lane / 16 compares the four bytes at P + 4 * (lane % 16).  A way that is
+// empty, not before P or more than kWideHist back counts as no match, and
+// nothing from end_lim on is compared.  A way that holds for all 64 bytes goes
+// on with the whole wave.
+__device__ __forceinline__ DeepHit deep_measure(const uint32_t *d, uint32_t P, uint32_t blo, uint32_t bhi, uint32_t end_lim,
+                                                uint32_t lane)
+{
+    const uint32_t way = lane >> 4, k4 = (lane & 15u) * 4u;
+    const uint32_t pair = (way & 2u) ? bhi : blo;
+    const uint32_t cand = (way & 1u) ? pair >> 16 : pair & 0xFFFFu;
+    const uint32_t c = cand - 1;
+    const uint32_t i = P + k4;
+    const bool wok = cand != 0u && c < P && P - c <= kWideHist && i < end_lim;
+    uint32_t nb = 0;
+    if (wok) {
+        const uint32_t x = wide_rd32(d, i) ^ wide_rd32(d, c + k4);  // c + k4 < i < end_lim: inside the window
+        nb = min(x ? uint32_t(__builtin_ctz(x)) >> 3 : 4u, end_lim - i);
+    }
+    const uint64_t b1 = __ballot(nb >= 1), b2 = __ballot(nb >= 2), b3 = __ballot(nb >= 3), b4 = __ballot(nb >= 4);
+    DeepHit best{0, 0};
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) {
+        const uint32_t wp = w & 2u ? bhi : blo;
+        const uint32_t wc = (w & 1u ? wp >> 16 : wp & 0xFFFFu) - 1;  // read only where the way matched
+        const uint32_t open = ~uint32_t(b4 >> (16 * w)) & 0xFFFFu;   // its lanes short of four bytes
+        uint32_t len;
+        if (open) {
+            const uint32_t at = 16 * w + uint32_t(__builtin_ctz(open));
+            len = 4 * (at & 15u) + uint32_t((b1 >> at) & 1u) + uint32_t((b2 >> at) & 1u) + uint32_t((b3 >> at) & 1u);
+        } else {
+            len = 64;
+            for (;;) {  // forwards to end_lim at most (wc < P: the source stays in the window)
+                const uint32_t j = P + len + lane;
+                const bool eq = j < end_lim && wide_rd8(d, j) == wide_rd8(d, wc + len + lane);
+                const uint64_t mm = __ballot(!eq);
+                if (!mm) {
+                    len += 64;
+                    continue;
+                }
+                len += uint32_t(__ffsll((unsigned long long)mm) - 1);
+                break;
+            }
+        }
+        if (len > best.len || (len == best.len && len && wc > best.c)) best = DeepHit{len, wc};
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(64) void k_lz_seq_deep(const Batch B)
+{
+    __shared__ DeepLds L;
+    const uint32_t lane = threadIdx.x, g = blockIdx.x;
+    if (g >= B.nsegs) return;
+    const Seg S = B.segs[g];
+    const uint32_t n = S.len, hist = min(uint32_t(S.hist), kWideHist), W = hist + n;  // W <= kWideWin
+    const uint8_t *win = B.base + S.src - hist;  // the plan keeps this inside the segment's block
+    // the window into LDS as k_lz_seq_wide stages it: nothing before win or from win + W on is read
+    const uint32_t nfull = W >> 4;
+    const uint32_t nbulk = nfull & ~511u;
+    for (uint32_t i0 = 0; i0 < nbulk; i0 += 64 * 8) {
+        uint4 v[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) __builtin_memcpy(&v[j], win + 16 * (i0 + 64 * j + lane), 16);
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) *reinterpret_cast<uint4 *>(&L.data[4 * (i0 + 64 * j + lane)]) = v[j];
+    }
+    for (uint32_t i = nbulk + lane; i < nfull; i += 64) {
+        uint4 v;
+        __builtin_memcpy(&v, win + 16 * i, 16);
+        *reinterpret_cast<uint4 *>(&L.data[4 * i]) = v;
+    }
+    const uint32_t tail = W & 15u;
+    if (lane < (tail ? 8u : 4u)) L.data[4 * nfull + lane] = 0;  // at most kWideWin / 4 + 4 words: a tail means W < kWideWin
+    for (uint32_t i = lane; i < (1u << kDeepBucketBits) / 2; i += 64) reinterpret_cast<uint4 *>(L.tab)[i] = make_uint4(0, 0, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < tail) reinterpret_cast<uint8_t *>(L.data)[16 * nfull + lane] = win[16 * nfull + lane];
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // every position of the history into the table, ascending by steps of 64
+    // positions, so a bucket's ways are its latest (short of what one step's
+    // lanes lose to each other).  hist is a multiple of the segment size.
+    for (uint32_t j0 = 0; j0 < hist; j0 += 64) {
+        const uint32_t pos = j0 + lane;
+        const uint32_t h = deep_hash(wide_rd32(L.data, pos));
+        const uint64_t old = L.tab[h];
+        __builtin_amdgcn_wave_barrier();
+        L.tab[h] = old << 16 | (pos + 1);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t start_lim = hist + min(n >= 4 ? n - 3 : 0u, S.rem > 12 ? S.rem - 12 : 0u);
+    const uint32_t end_lim = hist + min(n, S.rem > 5 ? S.rem - 5 : 0u);
+    uint2 *rec = B.recs + uint64_t(g) * kRecCap;
+    uint32_t cursor = hist, anchor = hist, nrec = 0;
+    while (cursor < start_lim) {  // the cursor moves forward every turn: at most n turns
+        const uint32_t stride = 1u + ((cursor - anchor) >> kSkipShift);
+        const uint32_t p = cursor + lane * stride;
+        const bool valid = p < start_lim;
+        const uint32_t v = valid ? wide_rd32(L.data, p) : 0u;
+        const uint32_t h = deep_hash(v);
+        const uint64_t old = valid ? L.tab[h] : 0ull;
+        bool ok = false;
+#pragma unroll
+        for (uint32_t w = 0; w < 4; ++w) {
+            const uint32_t cand = uint32_t(old >> (16 * w)) & 0xFFFFu, c = cand - 1;
+            ok = ok || (cand != 0u && c < p && p - c <= kWideHist && wide_rd32(L.data, c) == v);
+        }
+        const uint64_t m = __ballot(ok);
+        __builtin_amdgcn_wave_barrier();
+        if (!m) {
+            if (valid) L.tab[h] = old << 16 | (p + 1);
+            cursor += 64 * stride;
+            continue;
+        }
+        const uint32_t f = uint32_t(__ffsll((unsigned long long)m) - 1);
+        uint32_t q = cursor + f * stride;
+        DeepHit hit = deep_measure(L.data, q, uint32_t(__builtin_amdgcn_readlane(int(uint32_t(old)), int(f))),
+                                   uint32_t(__builtin_amdgcn_readlane(int(uint32_t(old >> 32)), int(f))), end_lim, lane);
+        uint32_t cq = hit.c, len = hit.len;  // len >= 4: lane f verified a way, and q + 4 <= end_lim
+        for (bool looked = false;; looked = true) {
+            // backwards over what the stride skipped (or, after a look, over
+            // the byte it left): the destination not past the last match's
+            // end, the source not past the window's start
+            uint32_t moved = 0;
+            for (;;) {
+                const uint32_t room = min(q - anchor, cq);
+                if (!room) break;
+                const uint32_t k = lane + 1;
+                const bool eq = k <= room && wide_rd8(L.data, q - k) == wide_rd8(L.data, cq - k);
+                const uint64_t mm = __ballot(!eq);
+                const uint32_t run = mm ? uint32_t(__ffsll((unsigned long long)mm) - 1) : 64u;
+                const uint32_t back = min(run, room);
+                q -= back;
+                cq -= back;
+                len += back;
+                moved += back;
+                if (back < 64) break;
+            }
+            if (moved || looked) break;
+            // the lazy look: while the position after q has a strictly longer
+            // match, q's byte stays a literal
+            bool took = false;
+            while (len < kDeepLazyMax && q + 1 < start_lim) {
+                // q did not move back: at stride 1 q + 1 is the position lane fl probed, and that lane
+                // holds its bucket (read before this step's inserts, as a read from the table here is)
+                const uint32_t fl = q + 1 - cursor;
+                uint32_t lo1, hi1;
+                if (stride == 1 && fl < 64) {
+                    lo1 = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(old)), int(fl)));
+                    hi1 = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(old >> 32)), int(fl)));
+                } else {
+                    const uint32_t h1 = deep_hash(wide_rd32(L.data, q + 1));
+                    const uint64_t b1 = L.tab[uint32_t(__builtin_amdgcn_readfirstlane(int(h1)))];
+                    lo1 = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(b1))));
+                    hi1 = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(b1 >> 32))));
+                }
+                const DeepHit nx = deep_measure(L.data, q + 1, lo1, hi1, end_lim, lane);
+                if (nx.len <= len) break;
+                q += 1;
+                cq = nx.c;
+                len = nx.len;
+                took = true;
+            }
+            if (!took) break;
+        }
+        if (lane == 0) rec[nrec] = make_uint2((q - hist) | ((q - cq) << 16), len);
+        ++nrec;
+        if (valid && p < q + len) L.tab[h] = old << 16 | (p + 1);
+        __builtin_amdgcn_wave_barrier();
+        anchor = cursor = q + len;
+    }
+    if (lane == 0) {
+        B.nrec[g] = nrec;
+        B.trail[g] = W - anchor;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 static cdc::AesTables g_tab;
@@ -1554,7 +1763,7 @@ extern "C" int cdc_encode_device_level(int device, const void *d_base, const uin
 {
     if ((n && (!d_base || !offsets || !lens || !out_offsets)) || (key && !random) || !d_out) return CDC_E_INVALID;
     if (device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;
-    if (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE) return CDC_E_INVALID;
+    if (!cdc::level_ok(level)) return CDC_E_INVALID;
     // the selector: 0 none, 2 GZIP, every other value LZ4
     const int mode = compress == CDC_COMPRESS_GZIP ? 2 : compress ? 1 : 0;
     const bool gzip = mode == 2;
@@ -1807,7 +2016,7 @@ extern "C" uint64_t cdc_gzip_stream_bound(uint64_t len) { return dfl::stream_pie
 
 extern "C" int cdc_gzip_stream_set_level(cdc_gzip_stream *S, int level)
 {
-    if (!S || (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE)) return CDC_E_INVALID;
+    if (!S || (!cdc::level_ok(level))) return CDC_E_INVALID;
     std::lock_guard<std::mutex> lk(S->mu);
     if (!S->first || S->closed) return CDC_E_INVALID;  // a member is written at one level
     S->level = level;

@@ -9,6 +9,7 @@
 
 #include "cdc_crypto_dev.h"
 #include "deflate_enc.h"
+#include "plakar_cdc.h"  // CDC_LEVEL_*
 
 namespace enc {
 
@@ -111,6 +112,7 @@ static_assert(kDflThreads == 256 && dfl::kSeg == kSegLZ && kBlockLZ % dfl::kSpan
 // their host stubs (the device code stays in cdc_encode.hip's code object).
 __global__ __launch_bounds__(kSeqWaves * 64) void k_lz4_seq(const Batch B);
 __global__ __launch_bounds__(64) void k_lz_seq_wide(const Batch B);  // a wave per segment and workgroup
+__global__ __launch_bounds__(64) void k_lz_seq_deep(const Batch B);  // the same, four candidates per bucket and a lazy look
 __global__ __launch_bounds__(kDflThreads) void k_dfl_size(const Batch B);
 __global__ __launch_bounds__(kDflThreads) void k_dfl_emit(const Batch B);
 
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(kDflThreads) void k_dfl_emit(const Batch B);
 inline void launch_seq(const Batch &Bt, int level, size_t ng, hipStream_t s)
 {
     if (!ng) return;
-    if (level) hipLaunchKernelGGL(k_lz_seq_wide, dim3(uint32_t(ng)), dim3(64), 0, s, Bt);
+    if (level == CDC_LEVEL_BEST) hipLaunchKernelGGL(k_lz_seq_deep, dim3(uint32_t(ng)), dim3(64), 0, s, Bt);
+    else if (level) hipLaunchKernelGGL(k_lz_seq_wide, dim3(uint32_t(ng)), dim3(64), 0, s, Bt);
     else hipLaunchKernelGGL(k_lz4_seq, dim3(uint32_t((ng + kSeqWaves - 1) / kSeqWaves)), dim3(kSeqWaves * 64), 0, s, Bt);
 }
 

@@ -216,6 +216,9 @@ int decode_checked(int device, const void *d_in, const uint64_t *offsets, const 
                    int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_out, uint64_t out_cap,
                    uint64_t *out_offsets, int32_t *status, void *stream, double *decode_s, double *verify_s);
 
+// The compression levels every entry point takes (CDC_LEVEL_*): any other value is CDC_E_INVALID.
+inline bool level_ok(int level) { return level == CDC_LEVEL_FAST || level == CDC_LEVEL_WIDE || level == CDC_LEVEL_BEST; }
+
 // cdc_packer.cpp: in-place serialization for the backup pipeline's sinks
 int packer_seal(cdc_packer *p, int64_t timestamp, const uint8_t **data, uint64_t *len);
 void packer_reserve(cdc_packer *p, uint64_t max_blob);

@@ -565,6 +565,17 @@ extern "C" int cdc_transcode_device(int device, const void *d_in, const uint64_t
                                     const uint8_t *random, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
                                     int32_t *status, void *stream)
 {
+    return cdc_transcode_device_level(device, d_in, offsets, lens, n, src, dst, checksums, random, d_out, out_cap,
+                                      out_offsets, status, CDC_LEVEL_FAST, stream);
+}
+
+extern "C" int cdc_transcode_device_level(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
+                                          uint32_t n, const cdc_codec *src, const cdc_codec *dst,
+                                          const uint8_t *checksums, const uint8_t *random, uint8_t *d_out,
+                                          uint64_t out_cap, uint64_t *out_offsets, int32_t *status, int level,
+                                          void *stream)
+{
+    if (!cdc::level_ok(level)) return CDC_E_INVALID;
     if (device < 0 || device >= cdc::kMaxDevices || !src || !dst || !out_offsets ||
         (n && (!d_in || !offsets || !lens || !status)) || (!d_out && out_cap) || (dst->key && !random))
         return CDC_E_INVALID;
@@ -646,8 +657,8 @@ extern "C" int cdc_transcode_device(int device, const void *d_in, const uint64_t
                                  sst.data(), s);
             break;
         case tplan::kPathReencode:
-            st = cdc_encode_device(device, C.plain.data(), p_off, p_len, m, dst->compress, dst->key, p_rnd, out, out_cap,
-                                   soo.data(), stream);
+            st = cdc_encode_device_level(device, C.plain.data(), p_off, p_len, m, dst->compress, dst->key, p_rnd, out,
+                                         out_cap, soo.data(), level, stream);
             break;
         }
     }

@@ -233,7 +233,7 @@ extern "C" int cdc_zip_pieces_device_level(int device, const void *d_src, uint64
                                            uint64_t out_cap, cdc_zip_piece_out *outs, uint64_t *total, int level,
                                            void *stream)
 {
-    if (level != CDC_LEVEL_FAST && level != CDC_LEVEL_WIDE) return CDC_E_INVALID;
+    if (!cdc::level_ok(level)) return CDC_E_INVALID;
     if (!total || (n && (!pieces || !outs))) return CDC_E_INVALID;
     *total = 0;
     if (device < 0 || device >= cdc::kMaxDevices) return CDC_E_INVALID;

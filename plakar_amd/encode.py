@@ -166,7 +166,8 @@ def encode_device(base, offsets, lens, out, key=None, compress=True, random=None
     byte offsets/lengths (sequences or numpy arrays) into the device tensor
     `out`; returns the n + 1 output offsets (int64 numpy array).  `compress`:
     False, True (an LZ4 frame) or "GZIP" (a gzip member).  `level`: 0 (matches
-    inside 8-KiB segments) or 1 (from up to 32 KiB before the segment)."""
+    inside 8-KiB segments), 1 (from up to 32 KiB before the segment) or 9 (the
+    same window, the longest of four candidates and a lazy parse: the smallest)."""
     import torch
     sel = _sel(compress)
     level = _lib.level_code(level)

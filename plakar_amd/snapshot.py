@@ -304,13 +304,24 @@ class BackupSession:
     cdc_backup_files (reads + object SHA-256, cut points, chunk SHA-256 +
     histograms, dedup, Encode, `packers` concurrent packerJob workers,
     snapshot/snapshot.go:51-92).  `level`: Encode's match search in this
-    session's runs (0, or 1: a 32-KiB window, smaller blobs; cdc_backup_set_level)."""
+    session's runs (0; 1: a 32-KiB window, smaller blobs; 9: four candidates per
+    bucket and a lazy parse, the smallest; cdc_backup_set_level)."""
 
     def __init__(self, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
                  packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, level=0):
         import ctypes
+        from . import _lib
+        level = _lib.level_code(level)  # ValueError for any value but 0, 1 and 9
+        o = self._opts(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp)
+        self._h = ctypes.c_void_p()
+        _lib.check(_lib.lib().cdc_backup_new(int(dev), ctypes.byref(o), ctypes.byref(self._h)), "cdc_backup_new")
+        if level:
+            _lib.check(_lib.lib().cdc_backup_set_level(self._h, level), "cdc_backup_set_level")
+
+    def _opts(self, repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp):
+        """The cdc_backup_opts of these arguments; the buffers it points to stay with self."""
+        import ctypes
         from . import _lib, packer as packer_mod
-        level = _lib.level_code(level)  # ValueError for any value but 0 and 1
         repo = repo or Repository()
         cfg = repo.Chunking
         opts = chunkers.ChunkerOpts(MinSize=int(cfg.MinSize), NormalSize=int(cfg.NormalSize),
@@ -334,10 +345,14 @@ class BackupSession:
             ks = sorted(bytes(k) for k in known)
             knownbuf = ctypes.create_string_buffer(b"".join(ks), 32 * len(ks))
             o.known, o.nknown = ctypes.cast(knownbuf, ctypes.c_void_p), len(ks)
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib().cdc_backup_new(int(dev), ctypes.byref(o), ctypes.byref(self._h)), "cdc_backup_new")
-        if level:
-            _lib.check(_lib.lib().cdc_backup_set_level(self._h, level), "cdc_backup_set_level")
+        self._keep = (keybuf, knownbuf)
+        return o
+
+    def _files(self, arr, n, fcb, pcb, st):
+        """The native call of one run: cdc_backup_files on the session's context."""
+        import ctypes
+        from . import _lib
+        return _lib.lib().cdc_backup_files(self._h, arr, n, fcb, pcb, None, ctypes.byref(st)), "cdc_backup_files"
 
     def run(self, paths, keep_packfiles=True, content_type=None):
         """Back up the files: (objects, packfiles, stats), as backup_files.
@@ -404,11 +419,11 @@ class BackupSession:
         gc_was = gc.isenabled()
         gc.disable()
         try:
-            rc = _lib.lib().cdc_backup_files(self._h, arr, n, fcb, pcb, None, ctypes.byref(st))
+            rc, what = self._files(arr, n, fcb, pcb, st)
         finally:
             if gc_was:
                 gc.enable()
-        _lib.check(rc, "cdc_backup_files")
+        _lib.check(rc, what)
         if errors:
             raise errors[0]
         stats = {name: getattr(st, name) for name, _ in _lib.cdc_backup_stats._fields_}
@@ -433,17 +448,38 @@ class BackupSession:
             pass
 
 
+class _BackupRun(BackupSession):
+    """One backup without a session: cdc_backup_run_level (new + files + free
+    in one native call) behind BackupSession.run's callbacks."""
+
+    def __init__(self, repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp, dev, level):
+        from . import _lib
+        self._level = _lib.level_code(level)
+        self._dev = int(dev)
+        self._o = self._opts(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp)
+        self._h = True  # nothing to free: the native call frees what it opens
+
+    def _files(self, arr, n, fcb, pcb, st):
+        import ctypes
+        from . import _lib
+        return _lib.lib().cdc_backup_run_level(self._dev, arr, n, ctypes.byref(self._o), fcb, pcb, None, ctypes.byref(st),
+                                               self._level), "cdc_backup_run_level"
+
+    def close(self):
+        self._h = None
+
+
 def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
                  packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, keep_packfiles=True, level=0):
-    """One backup of a list of files through the native pipeline (a
-    BackupSession for this call only).  known: iterable of 32-byte digests
+    """One backup of a list of files through the native pipeline
+    (cdc_backup_run_level: a context for this call only; `level` as
+    BackupSession's).  known: iterable of 32-byte digests
     already in the repository (not stored again).  Returns (objects,
     packfiles, stats): one Object per path in order (entropy and
     Distribution computed here from the device histograms, as chunkify_batch
     does), the serialised packfiles in the order the packers flushed them,
     and the per-stage stats of cdc_backup_stats."""
-    with BackupSession(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp,
-                       dev, level) as s:
+    with _BackupRun(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp, dev, level) as s:
         return s.run(paths, keep_packfiles)
 
 

@@ -62,8 +62,8 @@ def transcode_size(length, src_encrypted, dst_encrypted):
 
 
 def transcode_device(base, offsets, lens, out, src=(None, "LZ4"), dst=(None, "LZ4"), checksums=None, random=None,
-                     device=0, stream=None):
-    """cdc_transcode_device over torch uint8 tensors: the stored blobs at
+                     device=0, stream=None, level=0):
+    """cdc_transcode_device_level over torch uint8 tensors: the stored blobs at
     base[offsets[i]:offsets[i] + lens[i]], written by a repository with the codec
     `src` = (key, compression), as blobs of a repository with the codec `dst`,
     packed into `out`.  Returns (out_offsets, status): n + 1 int64 offsets and n
@@ -73,8 +73,11 @@ def transcode_device(base, offsets, lens, out, src=(None, "LZ4"), dst=(None, "LZ
     Raises CdcError(CDC_E_NOSPACE) when `out` is too small (.needed: the bytes
     to retry with).  Without checksums and with the same compression on both
     sides nothing is inflated: an encrypted source is authenticated by its GCM
-    tags, an unencrypted one is copied unvalidated."""
+    tags, an unencrypted one is copied unvalidated.  level: the match search of
+    the re-encode path (0, 1 or 9, as encode.encode_device); the other paths
+    ignore it."""
     import torch
+    level = _lib.level_code(level)
     ensure_init()
     n = len(lens)
     (skey, scomp), (dkey, dcomp) = _codec(src), _codec(dst)
@@ -97,12 +100,13 @@ def transcode_device(base, offsets, lens, out, src=(None, "LZ4"), dst=(None, "LZ
         random = None
     sc, dc = _lib.cdc_codec(scomp, skey), _lib.cdc_codec(dcomp, dkey)
     s = stream if stream is not None else torch.cuda.current_stream(device)
-    rc = lib().cdc_transcode_device(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs_a, ctypes.c_uint64),
-                                    _ptr(lens_a, ctypes.c_uint64), n, ctypes.byref(sc), ctypes.byref(dc), sums, random,
-                                    ctypes.c_void_p(out.data_ptr()), out.numel(), _ptr(oo_a, ctypes.c_uint64),
-                                    _ptr(st_a, ctypes.c_int32), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().cdc_transcode_device_level(int(device), ctypes.c_void_p(base.data_ptr()), _ptr(offs_a, ctypes.c_uint64),
+                                          _ptr(lens_a, ctypes.c_uint64), n, ctypes.byref(sc), ctypes.byref(dc), sums,
+                                          random, ctypes.c_void_p(out.data_ptr()), out.numel(),
+                                          _ptr(oo_a, ctypes.c_uint64), _ptr(st_a, ctypes.c_int32), level,
+                                          ctypes.c_void_p(s.cuda_stream))
     if rc < 0:
-        err = CdcError(rc, "cdc_transcode_device")
+        err = CdcError(rc, "cdc_transcode_device_level")
         err.needed = int(oo_a[n]) if rc == _lib.CDC_E_NOSPACE else None
         raise err
     return oo_a.astype(np.int64), st_a
@@ -119,14 +123,14 @@ def _first_cap(lens, src, dst):
                for n in lens)
 
 
-def _transcode_grow(base, offs, lens, src, dst, checksums, random, device):
+def _transcode_grow(base, offs, lens, src, dst, checksums, random, device, level=0):
     import torch
     cap = max(_first_cap(lens, src, dst), 1 << 16)
     while True:
         out = torch.empty(cap, dtype=torch.uint8, device=base.device)
         try:
             oo, st = transcode_device(base, offs, lens, out, src=src, dst=dst, checksums=checksums, random=random,
-                                      device=device)
+                                      device=device, level=level)
             return out, oo, st
         except CdcError as e:
             if e.status != _lib.CDC_E_NOSPACE or e.needed <= cap:
@@ -134,14 +138,15 @@ def _transcode_grow(base, offs, lens, src, dst, checksums, random, device):
             cap = e.needed
 
 
-def transcode_blobs(blobs, src=(None, "LZ4"), dst=(None, "LZ4"), checksums=None, random=None, device=0):
+def transcode_blobs(blobs, src=(None, "LZ4"), dst=(None, "LZ4"), checksums=None, random=None, device=0, level=0):
     """Transcode host byte buffers (upload, one transcode_device, download): a
     list with each blob's new encoding (bytes), or a TranscodeError in the
-    place of a blob that failed."""
+    place of a blob that failed.  level: as transcode_device."""
+    level = _lib.level_code(level)
     if not len(blobs):
         return []
     base, offs, lens = _upload(blobs, device)
-    out, oo, st = _transcode_grow(base, offs, lens, src, dst, checksums, random, device)
+    out, oo, st = _transcode_grow(base, offs, lens, src, dst, checksums, random, device, level)
     host = out[:int(oo[-1])].cpu().numpy()
     return [TranscodeError(int(st[i]), f"blob {i}") if st[i] else host[oo[i]:oo[i + 1]].tobytes()
             for i in range(len(blobs))]
@@ -169,7 +174,8 @@ class SyncSession:
     failures is not empty."""
 
     def __init__(self, src_key=None, src_compression="LZ4", dst_key=None, dst_compression="LZ4", verify=True,
-                 known=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0):
+                 known=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0, level=0):
+        self.level = _lib.level_code(level)  # the re-encode path's match search (0, 1 or 9)
         self.src, self.dst = (src_key, src_compression), (dst_key, dst_compression)
         _codec(self.src), _codec(self.dst)  # ValueError for a bad key or compression name
         self.path = path_of(self.src, self.dst)
@@ -231,7 +237,7 @@ class SyncSession:
                 torch.cuda.synchronize(dev)
                 t2 = time.perf_counter()
                 sums = [b[0][1] for b in batch] if self.verify else None
-                out, oo, st = _transcode_grow(base, offs[:-1], lens, self.src, self.dst, sums, None, self.device)
+                out, oo, st = _transcode_grow(base, offs[:-1], lens, self.src, self.dst, sums, None, self.device, self.level)
                 t3 = time.perf_counter()
                 got = out[:int(oo[-1])].cpu().numpy()
                 t4 = time.perf_counter()

@@ -25,7 +25,8 @@ readback and a synchronise per entry), timed once.
 
 --level 1: tar.gz and zip are written with the wide match search
 (cdc_archive_set_level), and level 0 runs beside it in the same process: its
-GiB/s and archive size are the *_l0_* figures."""
+GiB/s and archive size are the *_l0_* figures.  --level 9 (four candidates per
+bucket and a lazy parse) runs levels 0 and 1 beside it: *_l0_* and *_l1_*."""
 import argparse
 import json
 import os
@@ -39,6 +40,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def lower_levels(level):
+    """The levels that run beside --level in the same process."""
+    return {0: (), 1: (0,), 9: (0, 1)}[level]
 
 
 def zip_sets(a):
@@ -73,7 +79,7 @@ def zip_sets(a):
             line = dict(set=name, reps=a.reps, files=len(paths), file_bytes=int(data.size), level=a.level)
             for fmt in ("zip", "tarball"):
                 out = os.path.join(work, "out.zip" if fmt == "zip" else "out.tar.gz")
-                for lv in ((0, a.level) if a.level else (0,)):  # --level's run last: its file is the one read back
+                for lv in (lower_levels(a.level) + (a.level,)):  # --level's run last: its file is the one read back
                     best = None
                     with (archive.ZipSession(key=key, level=lv) if fmt == "zip"
                           else archive.ArchiveSession(key=key, format=fmt, level=lv)) as s:
@@ -85,8 +91,8 @@ def zip_sets(a):
                             if best is None or st["wall_s"] < best["wall_s"]:
                                 best = st
                     if lv != a.level:  # level 0 beside --level 1: speed and size
-                        line.update({f"{fmt}_l0_gibs": data.size / best["wall_s"] / 2**30,
-                                     f"{fmt}_l0_output_bytes": best["output_bytes"]})
+                        line.update({f"{fmt}_l{lv}_gibs": data.size / best["wall_s"] / 2**30,
+                                     f"{fmt}_l{lv}_output_bytes": best["output_bytes"]})
                         continue
                     line[f"{fmt}_gibs"] = data.size / best["wall_s"] / 2**30
                     line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})
@@ -137,8 +143,9 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--tmp", default=None, help="directory for the files (default: a temporary one)")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--level", type=int, default=0, choices=(0, 1),
-                    help="the match search of tar.gz and zip (1: a 32-KiB window); level 0 is then run beside it (*_l0_*)")
+    ap.add_argument("--level", type=int, default=0, choices=(0, 1, 9),
+                    help="the match search of tar.gz and zip (1: a 32-KiB window; 9: and four candidates per bucket, a "
+                         "lazy parse); the lower levels are then run beside it (*_l0_*, *_l1_*)")
     a = ap.parse_args()
     if a.format == "zip":
         return zip_sets(a)
@@ -172,7 +179,7 @@ def main():
             tar_path = os.path.join(work, "out.tar")
             for fmt in ("tar", "tarball"):
                 out = tar_path if fmt == "tar" else os.path.join(work, "out.tar.gz")
-                for lv in ((0, a.level) if a.level and fmt == "tarball" else (a.level,)):  # --level's run last
+                for lv in (lower_levels(a.level) + (a.level,) if fmt == "tarball" else (a.level,)):  # --level's run last
                     best = None
                     with archive.ArchiveSession(key=key, format=fmt, level=lv) as s:
                         for p in packs:
@@ -183,8 +190,8 @@ def main():
                             if best is None or st["wall_s"] < best["wall_s"]:
                                 best = st
                     if lv != a.level:  # level 0 beside --level 1: speed and size
-                        line.update({f"{fmt}_l0_gibs": best["stream_bytes"] / best["wall_s"] / 2**30,
-                                     f"{fmt}_l0_output_bytes": best["output_bytes"]})
+                        line.update({f"{fmt}_l{lv}_gibs": best["stream_bytes"] / best["wall_s"] / 2**30,
+                                     f"{fmt}_l{lv}_output_bytes": best["output_bytes"]})
                         continue
                     line[f"{fmt}_gibs"] = best["stream_bytes"] / best["wall_s"] / 2**30
                     line.update({f"{fmt}_{k}": v for k, v in best.items() if k not in ("struct_size", "failed_entry")})

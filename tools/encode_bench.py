@@ -14,7 +14,9 @@ One JSON line per set:
 With --level 1 every label runs at both levels in the same process (level 1:
 the match search with a 32-KiB window, k_lz_seq_wide): the level-1 figures
 carry the suffix _l1, the round trip is checked at both levels, and liblz4's
-block size of the same chunks stands beside zlib's.
+block size of the same chunks stands beside zlib's.  With --level 9 all
+three levels run (level 9: four candidates per bucket and a lazy parse,
+k_lz_seq_deep), its figures with the suffix _l9.
 
 Per-kernel times come from a kernel trace of the same command
 (rocprofv3 --kernel-trace --stats -- python tools/encode_bench.py --gzip ...).
@@ -58,7 +60,7 @@ def gzip_sets(a):
             best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
         return r, best / 1e3
 
-    levels = (0, 1) if a.level else (0,)
+    levels = {0: (0,), 1: (0, 1), 9: (0, 1, 9)}[a.level]
     for name in a.sets.split(","):
         if name == "text":
             buf = torch.from_numpy(np.frombuffer(decode_bench.text_like(np, size), dtype=np.uint8).copy()).to(dev)
@@ -80,7 +82,7 @@ def gzip_sets(a):
             enc = torch.empty(cap, dtype=torch.uint8, device=dev)
             for lv in levels:
                 oo, enc_s = timed(lambda: encode.encode_device(buf, offs, lens, enc, key=k, compress=comp, level=lv))
-                tag = label.replace("+", "_") + ("_l1" if lv else "")
+                tag = label.replace("+", "_") + (f"_l{lv}" if lv else "")
                 line.update({f"{tag}_s": enc_s, f"{tag}_gibs": n / enc_s / 2**30, f"{tag}_bytes": int(oo[-1])})
                 if label in ("gzip+gcm", "lz4+gcm") and (lv or label == "gzip+gcm"):  # the round trip, on the device
                     out = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -108,8 +110,9 @@ def gzip_sets(a):
                 with ThreadPoolExecutor(a.host_threads) as pool:
                     # a chunk is at most one 4-MiB block: the block, and the frame's 19 bytes around it
                     line["host_liblz4_bytes"] = sum(pool.map(lz4_ref.lz4_block_size, plains)) + 19 * len(lens)
-                if "gzip_gcm_l1_s" in line:
-                    line["level1_gzip_gcm_over_host"] = host_s / line["gzip_gcm_l1_s"]
+                for lv in levels[1:]:
+                    if f"gzip_gcm_l{lv}_s" in line:
+                        line[f"level{lv}_gzip_gcm_over_host"] = host_s / line[f"gzip_gcm_l{lv}_s"]
         print(json.dumps(line), flush=True)
         del buf
 
@@ -124,7 +127,8 @@ def main():
     ap.add_argument("--sets", default="c1,c3,text")
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--no-host", action="store_true")
-    ap.add_argument("--level", type=int, default=0, choices=(0, 1), help="1: every label at both levels, level 1 as *_l1")
+    ap.add_argument("--level", type=int, default=0, choices=(0, 1, 9),
+                    help="1: every label at levels 0 and 1 (*_l1); 9: at 0, 1 and 9 (*_l9)")
     a = ap.parse_args()
     if a.gzip:
         a.reps = a.reps or 3
@@ -160,7 +164,7 @@ def main():
                 continue
             cap = sum(encode.encode_bound(x, comp, k is not None) for x in lens)
             out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            for lv in ((0, 1) if a.level and comp else (0,)):
+            for lv in ({1: (0, 1), 9: (0, 1, 9)}[a.level] if a.level and comp else (0,)):
                 encode.encode_device(t, offs, lens, out, key=k, compress=comp, level=lv)  # warm
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
