@@ -741,6 +741,117 @@ int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_
                       cdc_restore_stats *stats);
 void cdc_restore_free(cdc_restore *r);
 
+/* ---- check: a snapshot's chunks and object checksums -------------------------------
+ * `plakar check` (snapshot/check.go:56-113) and `plakar checksum`
+ * (cmd/plakar/subcommands/checksum/checksum.go:108-119) for the objects the
+ * caller supplies (it walks the snapshot, as for restore).
+ *
+ * digests[i] = SHA-256 of the concatenation of object i's segments
+ * seg[obj_seg0[i] .. obj_seg0[i+1]) of d_data.  Host arrays; d_digests device,
+ * 32 B per object, 16-byte aligned.  A segment is any (offset, length) in the
+ * buffer: any alignment, any length including 0; segments may repeat and
+ * overlap.  An object without segments, or with empty ones only, hashes to
+ * SHA-256("").  The bytes are hashed where they lie: only the 64-byte blocks
+ * that a segment boundary cuts are copied (cdc_assemble_device, into a seam
+ * area the library keeps).  Synchronous on `stream`.
+ * CDC_E_INVALID: a segment outside [0, len), a list that does not ascend to
+ * nsegs, an object of 2^61 bytes or more, a NULL argument (d_data may be NULL
+ * when len is 0) or a d_digests that is not 16-byte aligned; CDC_E_NOT_INIT
+ * before cdc_init; CDC_OK when n == 0.  Nothing is launched and d_digests is
+ * untouched unless CDC_OK or CDC_E_DEVICE comes back. */
+int cdc_object_digests_device(int device, const void *d_data, uint64_t len,
+                              const uint64_t *seg_off, const uint64_t *seg_len, uint64_t nsegs,
+                              const uint64_t *obj_seg0, uint32_t n, uint8_t *d_digests, void *stream);
+
+/* A check context, shaped like a restore context: Decode's configuration, the
+ * registered packfiles and their locator, streams and buffers kept across
+ * runs.  One cdc_check_files at a time per context. */
+typedef struct cdc_check_opts {
+    uint32_t struct_size;   /* sizeof(cdc_check_opts) */
+    int compress;           /* CDC_COMPRESS_NONE, _LZ4 or _GZIP */
+    const uint8_t *key;     /* 32-byte repository key, or NULL */
+    int fast;               /* check -fast: presence only, no device work */
+    int threads;            /* reader and host-hash threads (0: 8) */
+    uint64_t batch_bytes;   /* of file bytes per batch (0: 256 MiB; at most 1 GiB) */
+    uint64_t host_min_len;  /* 0: the model; else objects at least this long hash on the host */
+} cdc_check_opts;
+/* struct_size set, everything else 0. */
+void cdc_check_default_opts(cdc_check_opts *out);
+typedef struct cdc_check_file {
+    uint64_t nchunks;
+    const uint8_t *checksums;        /* 32 B per chunk (Chunk.Checksum) */
+    const uint32_t *lengths;         /* Chunk.Length */
+    const uint8_t *object_checksum;  /* 32 B, or NULL: compute only (plakar checksum) */
+} cdc_check_file;
+typedef struct cdc_check_result {
+    int index;              /* position in files */
+    int status;
+    int64_t bad_chunk;      /* the chunk `status` names, or -1 (none, or the object itself) */
+    int hashed;             /* 0 not hashed, 1 on the device, 2 on the host */
+    uint8_t checksum[32];   /* the computed object SHA-256 when hashed != 0 */
+    uint64_t size;          /* the sum of the chunk lengths */
+} cdc_check_result;
+typedef struct cdc_check_stats {
+    uint32_t struct_size;   /* set by the caller; at most that many bytes are written */
+    uint32_t reserved;
+    uint64_t files, failed_files, bytes, segments;  /* bytes: file bytes of the batches */
+    uint64_t distinct_blobs, decoded_blobs, encoded_bytes, decoded_bytes, batches, pieces;  /* as cdc_restore_stats */
+    uint64_t device_objects, device_bytes;  /* objects hashed by k_object_digest where their blobs lie */
+    uint64_t host_objects, host_bytes;      /* objects gathered, copied back and hashed on host threads */
+    uint64_t seam_bytes;                    /* copied for the device's objects (blocks a chunk boundary cuts) */
+    /* wall time of each stage, summed.  digest_s: the device's objects (runs planned, seam copies,
+     * k_object_digest, the digests back); d2h_s: the host's bytes gathered and copied back; hash_s: hashed */
+    double read_s, h2d_s, decode_s, verify_s, digest_s, d2h_s, hash_s;
+    double wall_s;
+} cdc_check_stats;
+typedef void (*cdc_check_file_fn)(void *ctx, const cdc_check_result *r);
+typedef struct cdc_check cdc_check;
+/* CDC_E_INVALID: NULL, a struct_size that is not this header's, a device
+ * outside 0..63, an unknown compress, threads outside 0..256, batch_bytes
+ * over 1 GiB; CDC_E_NOT_INIT before cdc_init (fast contexts too). */
+int cdc_check_new(int device, const cdc_check_opts *opts, cdc_check **out);
+int cdc_check_add_packfile(cdc_check *c, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
+int cdc_check_add_packfile_path(cdc_check *c, const char *path);
+/* Check n files from their chunk lists and object checksums.  Per batch of at
+ * most batch_bytes of file bytes (restore's plan): reader threads gather the
+ * batch's distinct encoded blobs, one upload, one Decode with SHA-256 and
+ * compare over the distinct blobs (restore's, with its slow path for a blob
+ * that decodes to more than its Length).  Then the objects are hashed: those
+ * the device takes by k_object_digest over the places of their chunks in the
+ * plaintext buffer (no image is assembled; 32 bytes per object come back),
+ * those the host takes are gathered by cdc_assemble_device into a staging
+ * image, copied back once and hashed on `threads` threads.  The split is
+ * cdc_chunk_digests_hybrid's model over the objects' lengths, or host_min_len.
+ * A file that spans batches is always hashed on the host, piece by piece as
+ * the pieces come back: the device keeps no midstate between batches.  Batch
+ * k + 1 is read and uploaded while batch k is on the device and batch k - 1's
+ * host-bound objects are hashed.
+ * on_file (may be NULL) is called once per file, from one library thread at a
+ * time, with (check.go:66-111):
+ *   CDC_OK          every chunk is found, decodes to its recorded Length with
+ *                   its SHA-256, and the object's SHA-256 equals
+ *                   object_checksum when one is given;
+ *   CDC_E_NOTFOUND  a chunk in no registered packfile: bad_chunk its index,
+ *                   hashed = 0, the file is not decoded (as restore does not).
+ *                   When a file has a missing chunk and an earlier damaged one
+ *                   the reference names the earlier one, this the missing one;
+ *   a blob's status a blob that cannot be read (CDC_E_IO), fails Decode, has
+ *                   the wrong Length or SHA-256 (CDC_E_MISMATCH): bad_chunk is
+ *                   the lowest index in the file with a failed blob, hashed =
+ *                   0; every file that uses the blob fails, and no other;
+ *   CDC_E_MISMATCH  with bad_chunk = -1 and hashed != 0: all chunks fine, the
+ *                   object's SHA-256 (in `checksum`) is not object_checksum.
+ * With opts.fast only the locator is asked (check.go:68-75): CDC_E_NOTFOUND
+ * with the first missing index, or CDC_OK; hashed = 0, nothing is read,
+ * uploaded or launched and stats.decoded_blobs is 0.  The reference compares
+ * the empty hasher's sum with the recorded checksum in that mode too
+ * (check.go:107), which fails every file with bytes; that is not reproduced.
+ * Returns CDC_OK, or the run's own first failure; CDC_E_INVALID (NULL context
+ * or files, a file with chunks and no arrays) before the device is touched. */
+int cdc_check_files(cdc_check *c, const cdc_check_file *files, int n, cdc_check_file_fn on_file, void *ctx,
+                    cdc_check_stats *stats);
+void cdc_check_free(cdc_check *c);
+
 /* ---- archive: a snapshot's entries as one tar or tar.gz stream -------------------
  * `plakar archive` (cmd/plakar/subcommands/archive/archive.go) for its tar and
  * tarball formats.  The caller supplies the entries (it walks the snapshot, as

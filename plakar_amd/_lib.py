@@ -157,6 +157,32 @@ class cdc_restore_stats(ctypes.Structure):
                                                "write_s", "wall_s")]
 
 
+class cdc_check_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
+                ("fast", ctypes.c_int), ("threads", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
+                ("host_min_len", ctypes.c_uint64)]
+
+
+class cdc_check_file(ctypes.Structure):
+    _fields_ = [("nchunks", ctypes.c_uint64), ("checksums", ctypes.c_void_p), ("lengths", ctypes.c_void_p),
+                ("object_checksum", ctypes.c_void_p)]
+
+
+class cdc_check_result(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_int), ("status", ctypes.c_int), ("bad_chunk", ctypes.c_int64),
+                ("hashed", ctypes.c_int), ("checksum", ctypes.c_uint8 * 32), ("size", ctypes.c_uint64)]
+
+
+class cdc_check_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("files", "failed_files", "bytes", "segments", "distinct_blobs",
+                                               "decoded_blobs", "encoded_bytes", "decoded_bytes", "batches", "pieces",
+                                               "device_objects", "device_bytes", "host_objects", "host_bytes",
+                                               "seam_bytes")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "digest_s", "d2h_s", "hash_s",
+                                               "wall_s")]
+
+
 class cdc_archive_opts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
                 ("verify", ctypes.c_int), ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
@@ -194,6 +220,7 @@ CDC_ARCHIVE_FILE, CDC_ARCHIVE_DIR = 0, 1
 ARCHIVE_DATA_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 ARCHIVE_ENTRY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)
 RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_restore_result))
+CHECK_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_check_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 
@@ -339,6 +366,16 @@ SIGNATURES = {
     "cdc_restore_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, RESTORE_FILE_FN,
                                          ctypes.c_void_p, _P(cdc_restore_stats)]),
     "cdc_restore_free": (None, [ctypes.c_void_p]),
+    "cdc_object_digests_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                                 _P(ctypes.c_uint64), ctypes.c_uint64, _P(ctypes.c_uint64),
+                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "cdc_check_default_opts": (None, [_P(cdc_check_opts)]),
+    "cdc_check_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_check_opts), _P(ctypes.c_void_p)]),
+    "cdc_check_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_check_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_check_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_check_file), ctypes.c_int, CHECK_FILE_FN,
+                                       ctypes.c_void_p, _P(cdc_check_stats)]),
+    "cdc_check_free": (None, [ctypes.c_void_p]),
     "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
     "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_new_zip": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),

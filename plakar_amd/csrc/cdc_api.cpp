@@ -28,6 +28,7 @@
 
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
+#include "hybrid_model.h"
 
 using namespace cdc;
 
@@ -1156,35 +1157,17 @@ double host_sha_rate()
     return rate;
 }
 
-// The host's share: the longest chunks, as many as balance the two sides.
-// Device: the longest chunk left to it (its chain, ~2.05 us per 64-B block).
-// Host: its chunks come back over PCIe in `parts` pieces while the threads
-// hash the pieces already landed, so its time is the first piece's copy plus
-// the slower of the copy of the rest and the hashing (bytes over `threads`
-// cores, the longest chunk's own chain at least).
+// The host's share: the longest chunks, as many as balance the two sides
+// (the model is hybrid_model.h's, which the check pipeline uses too), at this
+// host's measured SHA-256 rate.
 size_t hybrid_split(const std::vector<uint64_t> &sorted_desc, int threads, int parts)
 {
-    constexpr double kDevPerByte = 2.05e-6 / 64.0, kPcie = 40e9;
-    const double rate = host_sha_rate();
-    double best = 1e30, bytes = 0;
-    size_t k_best = 0;
-    const size_t n = std::min<size_t>(sorted_desc.size(), 1u << 16);
-    for (size_t k = 0; k <= n; ++k) {
-        const double dev = k < sorted_desc.size() ? double(sorted_desc[k]) * kDevPerByte : 0.0;
-        const double host =
-            k ? bytes / double(std::min<size_t>(size_t(parts), k)) / kPcie +
-                    std::max({double(sorted_desc[0]) / rate, bytes / (threads * rate), bytes / kPcie})
-              : 0.0;
-        const double t = std::max(dev, host);
-        if (t < best) {
-            best = t;
-            k_best = k;
-        }
-        if (k < n) bytes += double(sorted_desc[k]);
-    }
-    return k_best;
+    return hybrid::split(sorted_desc, threads, parts, host_sha_rate());  // hybrid_model.h
 }
 }  // namespace
+namespace cdc {
+double host_sha256_rate() { return host_sha_rate(); }
+}  // namespace cdc
 extern "C" {
 
 int cdc_chunk_digests_hybrid(int device, const void *const *d_data, const uint64_t *lens, int nbufs,

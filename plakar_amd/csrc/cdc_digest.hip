@@ -23,6 +23,7 @@
 
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
+#include "sha_blocks.h"
 
 namespace cdc {
 
@@ -410,6 +411,293 @@ __global__ __launch_bounds__(kDigestWaves * 64) void k_chunk_digest(const Digest
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_object_digest: SHA-256 of objects, each the concatenation of segments of
+// one buffer (Object.Checksum, snapshot/check.go:63-107: every chunk of a file
+// through a second hasher), hashed where the blobs lie.  The host has turned
+// every object into runs (check_plan.h): aligned-dword streams in the source
+// buffer or the seam area, every one but an object's last a multiple of 64
+// bytes, so a block's data words come from one run.  k_chunk_digest's
+// structure, with the object in the chunk's place: a producer wave and a round
+// wave per 64 lanes, the two-stage ring, loads two blocks ahead, one barrier
+// per block, the workgroup's queue handing objects out longest first.  The
+// producer walks an object's runs as it walks chunks (each with its own funnel
+// shift selector, loads clamped to the run's last dword; the next run's
+// descriptor is loaded when a run starts); the round wave carries the state
+// across runs and writes the digest after the object's last block, as it does
+// for a chunk.  Padding and the bit length come from the object's 64-bit total
+// (sha_blocks.h).  Whatever the lists say, reads stay inside the source buffer
+// and the seam area: run indices and runs are clipped.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void run_at(const ObjBatch &B, uint64_t r, const uint8_t *&base, uint64_t &off, uint64_t &n)
+{
+    const ObjRun R = B.runs[min<uint64_t>(r, B.nruns - 1u)];
+    const bool seam = (R.src >> 63) != 0;
+    base = seam ? B.seam : B.data;
+    const uint64_t cap = seam ? B.seam_len : B.len;
+    off = R.src & ~(1ull << 63);
+    n = R.bytes;
+    if (off > cap) {
+        off = 0;
+        n = 0;
+    } else if (n > cap - off) {
+        n = cap - off;
+    }
+}
+
+__device__ __forceinline__ void obj_at(const ObjBatch &B, uint64_t c, uint64_t &total, uint64_t &r0, uint64_t &rend)
+{
+    const ObjRec O = B.objs[c];
+    total = min<uint64_t>(O.total, shab::kMaxTotal);
+    r0 = min<uint64_t>(O.run0, B.nruns - 1u);
+    rend = r0 + min<uint64_t>(max<uint64_t>(O.nruns, 1u), B.nruns - r0);
+}
+
+__global__ __launch_bounds__(kDigestWaves * 64) void k_object_digest(const ObjBatch B)
+{
+    constexpr uint32_t kLanes = 64u * kDigestGroups;
+    __shared__ uint4 s_ring[kDigestGroups][kRingBytes / 16u];
+    __shared__ uint32_t s_meta[kDigestGroups][kShaRing][2][64];
+    __shared__ uint32_t s_any[kShaRing][kDigestGroups];
+    __shared__ uint32_t s_next;           // the workgroup's object queue (relative)
+    __shared__ uint64_t s_order[kSortCap];  // its objects longest first: (blocks << 32) | index
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t grp = wave % kDigestGroups;
+    const uint32_t role = wave / kDigestGroups;  // 0 producer, 1 rounds
+    uint4 *ring = s_ring[grp];
+    const uint32_t lane = threadIdx.x & 63u;
+    // objects per workgroup and the queue: as k_chunk_digest's chunks
+    const uint64_t total = B.n;
+    const uint64_t R = B.resident_lanes ? B.resident_lanes : 1u;
+    const uint64_t k = total > R ? (total + R - 1) / R : 1u;
+    const uint64_t C0 = uint64_t(blockIdx.x) * kLanes * k;
+    if (C0 >= total) return;  // whole workgroup: no barrier is left waiting
+    const uint64_t C1 = min(C0 + kLanes * k, total);
+    if (threadIdx.x == 0) s_next = kLanes;
+    const uint32_t nq = uint32_t(C1 - C0);
+    const bool sorted = nq > kLanes && nq <= kSortCap;
+    if (sorted) {
+        uint32_t m = kLanes;
+        while (m < nq) m <<= 1;
+        for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+            uint64_t t = 0, r0, rend;
+            if (i < nq) obj_at(B, C0 + i, t, r0, rend);
+            const uint64_t nb = min<uint64_t>(shab::blocks(t), 0xFFFFFFFFull);
+            s_order[i] = i < nq ? (nb << 32) | i : 0ull;  // padding sorts last (a real object has a block)
+        }
+        __syncthreads();
+        for (uint32_t size = 2; size <= m; size <<= 1) {
+            for (uint32_t stride = size >> 1; stride; stride >>= 1) {
+                for (uint32_t t = threadIdx.x; t < m / 2; t += blockDim.x) {
+                    const uint32_t i = 2 * stride * (t / stride) + t % stride, j = i + stride;
+                    const bool desc = (i & size) == 0;
+                    const uint64_t a = s_order[i], b = s_order[j];
+                    if ((a < b) == desc) {
+                        s_order[i] = b;
+                        s_order[j] = a;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    auto queued = [&](uint32_t q) -> uint64_t { return C0 + (sorted ? uint32_t(s_order[q]) : q); };
+
+    if (role == 0) {
+        const uint32_t *dummy = reinterpret_cast<const uint32_t *>(B.objs);  // a lane without a block reads the records
+        const uint32_t q0 = 64u * grp + lane;
+        // the load cursor: object lc of T bytes and onb blocks, at its block gb;
+        // run r of [., rend), rn bytes at rbase + roff, at the run's block lb
+        uint64_t lc = q0 < nq ? queued(q0) : C1, T = 0, onb = 0, gb = 0, r = 0, rend = 0, roff = 0, rn = 0, lb = 0;
+        const uint8_t *rbase = B.data;
+        constexpr uint32_t kHas = 1u, kResv = 2u;  // the cursor has an object; its next one is requested
+        uint32_t lst = lc < C1 ? kHas : 0u;
+        // the run after the cursor's, loaded when the cursor's starts
+        const uint8_t *pbase = B.data;
+        uint64_t poff = 0, pn = 0;
+        auto prefetch_run = [&]() __attribute__((always_inline)) {
+            if (r + 1u < rend) run_at(B, r + 1u, pbase, poff, pn);
+        };
+        if (lst & kHas) {
+            obj_at(B, lc, T, r, rend);
+            onb = shab::blocks(T);
+            run_at(B, r, rbase, roff, rn);
+            prefetch_run();
+        }
+        ChunkWords LA = chunk_words(rbase, roff, rn);
+        // the cursor's next object, taken from the queue (its record and first
+        // run loaded) one block before the current one's last
+        uint64_t cn = ~0ull, nT = 0, nr = 0, nrend = 0, noff = 0, nn = 0;
+        const uint8_t *nbase = B.data;
+        auto reserve = [&]() __attribute__((always_inline)) {
+            const uint32_t q = __hip_atomic_fetch_add(&s_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            cn = q < nq ? queued(q) : ~0ull;
+            if (cn != ~0ull) {
+                obj_at(B, cn, nT, nr, nrend);
+                run_at(B, nr, nbase, noff, nn);
+            }
+            lst |= kResv;
+        };
+        struct Blk {
+            uint32_t x[17];
+            uint32_t sel, crel, fl, bhi, blo;  // crel = kNoChunk: the lane has no block; fl: the object's last block
+            int32_t rb;                        // shab::remaining of the block
+        };
+        constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
+        auto issue = [&](Blk &k) __attribute__((always_inline)) {  // the cursor's block into k, then advance the cursor
+            const bool real = (lst & kHas) && rn != 0;
+            const uint32_t *q = real ? LA.q : dummy;
+            const uint64_t base = real ? 16u * lb : 0u, lim = real ? LA.lastq : 0u;
+#pragma unroll
+            for (int j = 0; j < 17; ++j) k.x[j] = q[min<uint64_t>(base + j, lim)];
+            k.sel = LA.sel;
+            k.crel = (lst & kHas) ? uint32_t(lc - C0) : kNoChunk;
+            k.rb = shab::remaining(T, gb);
+            k.fl = gb + 1u == onb ? 1u : 0u;
+            k.bhi = shab::bits_hi(T);
+            k.blo = shab::bits_lo(T);
+            if (lst & kHas) {
+                ++lb;
+                ++gb;
+                if (!(lst & kResv) && gb + 1u >= onb) reserve();
+                if (gb == onb) {
+                    if (cn != ~0ull) {
+                        lc = cn;
+                        T = nT;
+                        onb = shab::blocks(nT);
+                        gb = 0;
+                        r = nr;
+                        rend = nrend;
+                        rbase = nbase;
+                        roff = noff;
+                        rn = nn;
+                        lb = 0;
+                        LA = chunk_words(rbase, roff, rn);
+                        lst = kHas;
+                        prefetch_run();
+                    } else {
+                        lst = 0u;
+                    }
+                } else if (64u * lb >= rn && r + 1u < rend) {  // the run is used up (on a block boundary): the next one
+                    ++r;
+                    rbase = pbase;
+                    roff = poff;
+                    rn = pn;
+                    lb = 0;
+                    LA = chunk_words(rbase, roff, rn);
+                    prefetch_run();
+                }
+            }
+        };
+        auto step = [&](uint32_t it, const Blk &k) __attribute__((always_inline)) -> bool {
+            const bool live = k.crel != kNoChunk;
+            const bool last = live && k.fl != 0u;
+            uint32_t w[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) w[q] = __builtin_amdgcn_perm(k.x[q + 1], k.x[q], k.sel);
+            const int32_t rb = live ? k.rb : 128;
+            if (shab::has_padding(rb)) {  // the object's final block or two: data bytes, 0x80, zeros, bit length
+#pragma unroll
+                for (int q = 0; q < 16; ++q) w[q] = (w[q] & shab::keep_mask(rb, q)) | shab::pad_byte(rb, q);
+                if (shab::has_length(rb)) {
+                    w[14] = k.bhi;
+                    w[15] = k.blo;
+                }
+            }
+            const uint32_t stg = it & 1u;
+            uint4 *st = ring + stg * 1024u + lane;
+#pragma unroll
+            for (int q = 0; q < 16; q += 4) st[q * 16] = make_uint4(w[q], w[q + 1], w[q + 2], w[q + 3]);
+            uint32_t x4[4];
+#pragma unroll
+            for (int t = 16; t < 64; ++t) {
+                const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+                const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
+                const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
+                const uint32_t wt = w[t & 15] + s0 + w[(t + 9) & 15] + s1;
+                w[t & 15] = wt;
+                x4[t & 3] = wt;
+                if ((t & 3) == 3) st[(t / 4) * 64] = make_uint4(x4[0], x4[1], x4[2], x4[3]);
+            }
+            s_meta[grp][stg][0][lane] = k.crel;
+            s_meta[grp][stg][1][lane] = (live ? kMetaLive : 0u) | (last ? kMetaLast : 0u);
+            const bool any = __ballot(live) != 0;
+            if (lane == 0) s_any[stg][grp] = any ? 1u : 0u;
+            __syncthreads();
+            return (s_any[stg][0] | s_any[stg][kDigestGroups - 1]) != 0;
+        };
+        Blk b0, b1, b2;
+        issue(b0);
+        issue(b1);
+        for (uint32_t it = 0;; it += 3) {
+            issue(b2);
+            if (!step(it, b0)) break;
+            issue(b0);
+            if (!step(it + 1, b1)) break;
+            issue(b1);
+            if (!step(it + 2, b2)) break;
+        }
+    } else {  // role 1: the rounds, the state carried from an object's first block to its last
+        constexpr uint32_t kIV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                                     0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+        uint32_t h[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = kIV[j];
+        __builtin_amdgcn_s_setprio(3);
+        for (uint32_t it = 0;; ++it) {
+            __syncthreads();  // stage it filled
+            const uint32_t stg = it & 1u;
+            const uint32_t any = s_any[stg][0] | s_any[stg][kDigestGroups - 1];
+            const uint32_t m = s_meta[grp][stg][1][lane], crel = s_meta[grp][stg][0][lane];
+            const uint4 *st = ring + stg * 1024u + lane;
+            const uint4 v0 = st[0];
+            if (!any) break;
+            uint32_t a = h[0], b = h[1], cc = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+#pragma unroll
+            for (int q4 = 0; q4 < 16; ++q4) {
+                const uint4 v = q4 ? st[q4 * 64] : v0;
+                const uint32_t wq[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int t = 4 * q4 + j;
+                    const uint32_t S1 = xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25));
+                    const uint32_t ch = __builtin_amdgcn_bitop3_b32(e, f, g, 0xCA);
+                    const uint32_t t1 = hh + S1 + ch + kSha256K[t] + wq[j];
+                    const uint32_t S0 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22));
+                    const uint32_t mj = __builtin_amdgcn_bitop3_b32(a, b, cc, 0xE8);
+                    hh = g;
+                    g = f;
+                    f = e;
+                    e = d + t1;
+                    d = cc;
+                    cc = b;
+                    b = a;
+                    a = t1 + S0 + mj;
+                }
+            }
+            if (m & kMetaLive) {
+                h[0] += a;
+                h[1] += b;
+                h[2] += cc;
+                h[3] += d;
+                h[4] += e;
+                h[5] += f;
+                h[6] += g;
+                h[7] += hh;
+                if (m & kMetaLast) {  // the object's digest, then the next object from the IV
+                    uint4 *out = reinterpret_cast<uint4 *>(B.digests + (C0 + crel) * 32u);
+                    auto bswap = [](uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x00010203u); };
+                    out[0] = make_uint4(bswap(h[0]), bswap(h[1]), bswap(h[2]), bswap(h[3]));
+                    out[1] = make_uint4(bswap(h[4]), bswap(h[5]), bswap(h[6]), bswap(h[7]));
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) h[j] = kIV[j];
+                }
+            }
+        }
+    }
+}
+
 // Byte histograms, one wave per chunk (a wave takes chunks w, w + waves, ...):
 // the frequency count of entropy() (snapshot/backup.go:548-557).  Unlike the
 // SHA-256 chain a histogram has no order, so the wave reads its chunk
@@ -659,6 +947,23 @@ int launch_digests(const DigestBatch &DB, void *stream, int parts)
     DigestBatch D = DB;
     D.ind = nullptr;
     return launch_digest_kernels<false>(D, cap, hist, reinterpret_cast<hipStream_t>(stream), parts);
+}
+
+int launch_object_digests(const ObjBatch &B0, void *stream)
+{
+    if (B0.n == 0) return CDC_OK;
+    // object indices relative to a workgroup's first are u32; every object has a run
+    if (B0.n > 0xFFFFFFFFull || B0.nruns == 0 || !B0.runs || !B0.objs || !B0.digests ||
+        (reinterpret_cast<uintptr_t>(B0.digests) & 15u))
+        return CDC_E_INVALID;
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    ObjBatch B = B0;
+    B.resident_lanes = g_digest_lanes ? g_digest_lanes : uint64_t(device_cus(dev)) * 2u * 64u * kDigestGroups;
+    const uint32_t lanes_per_wg = 64u * kDigestGroups;
+    hipLaunchKernelGGL(k_object_digest, dim3(uint32_t((B.n + lanes_per_wg - 1) / lanes_per_wg)), dim3(kDigestWaves * 64),
+                       0, reinterpret_cast<hipStream_t>(stream), B);
+    return hipGetLastError() == hipSuccess ? CDC_OK : CDC_E_DEVICE;
 }
 
 // ---------------------------------------------------------------------------

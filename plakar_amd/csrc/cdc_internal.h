@@ -161,6 +161,35 @@ int launch_digests_many(const DigestBuf *bufs, uint32_t nbufs, void *stream);
 int launch_entropy(const uint32_t *d_hist, uint64_t rows, double *d_out, void *stream);
 int launch_arena_cuts(const uint64_t *d_meta, uint32_t nfiles, const cdc_result *d_res, const cdc_cut *d_cuts,
                       cdc_cut *d_out, void *stream);
+// k_object_digest: SHA-256 of n objects, each the concatenation of its runs
+// (check_plan.h: aligned-dword streams in the source buffer or the seam area,
+// every one but an object's last a multiple of 64 bytes).  Every object has at
+// least one run; digests is 16-byte aligned, 32 B per object.
+struct ObjRec {
+    uint64_t total, run0, nruns, reserved;
+};
+struct ObjRun {
+    uint64_t src, bytes;  // cplan::Run
+};
+struct ObjBatch {
+    const uint8_t *data;
+    uint64_t len;
+    const uint8_t *seam;
+    uint64_t seam_len;
+    const ObjRun *runs;
+    uint64_t nruns;
+    const ObjRec *objs;
+    uint64_t n;
+    uint8_t *digests;
+    uint64_t resident_lanes;  // set by launch_object_digests
+};
+int launch_object_digests(const ObjBatch &B, void *stream);
+// cdc_check.cpp: cdc_object_digests_device after its argument checks, for the
+// check pipeline too; *seam_bytes (may be NULL) receives the seam area's size.
+int object_digests(int device, const void *d_data, uint64_t len, const uint64_t *seg_off, const uint64_t *seg_len,
+                   uint64_t nsegs, const uint64_t *obj_seg0, uint32_t n, uint8_t *d_digests, void *stream,
+                   uint64_t *seam_bytes);
+double host_sha256_rate();  // cdc_api.cpp: one host core's SHA-256 bytes per second, measured once
 extern uint64_t g_digest_lanes;
 // The calling thread's scan mode for make_plan: -1 the default (static grid,
 // or CDC_SCAN_TASKS_PER_WAVE), k >= 0 the persistent scan with about k tasks

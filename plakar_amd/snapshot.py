@@ -484,6 +484,7 @@ def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", kn
 
 
 from .restore import RestoreSession, restore_files  # noqa: E402 - the read path, next to backup_files
+from .check import CheckSession, check_files  # noqa: E402 - and the check of what was written
 
 __all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
-           "RestoreSession", "restore_files"]
+           "RestoreSession", "restore_files", "CheckSession", "check_files"]
