@@ -364,6 +364,40 @@ int cdc_decode_device(int device, const void *d_in, const uint64_t *offsets, con
                       int compressed, const uint8_t *key, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
                       int32_t *status, void *stream);
 
+/* cdc_decode_device for the first upto[i] plaintext bytes of blob i: what a
+ * reader of a byte range needs (VFilep.Read, snapshot/vfs/vfilep.go:58-122,
+ * decodes the whole chunk for every call).  The decode chains are serial, so a
+ * walk that stops at upto[i] costs in proportion to upto[i].
+ *   The caller knows every blob's recorded length, so there is no sizing pass:
+ *   out_offsets (host, n + 1) is the exclusive sum of upto, computed before
+ *   anything is launched; out_cap < out_offsets[n] is CDC_E_NOSPACE with
+ *   nothing launched.  Blob i's prefix lands at d_out + out_offsets[i].
+ *   Nothing at or beyond d_out + out_offsets[n] is written: no scratch tail,
+ *   no compaction.  A failed blob leaves its own range undefined and no other.
+ *   The sequence (literal run, stored block, match) that crosses upto[i] is
+ *   cut to the byte and the walk ends there, CDC_OK.  What the stream holds
+ *   after it is not validated and need not be well formed: the rest of the
+ *   block, later blocks, the end mark, the LZ4 content checksum, the gzip
+ *   CRC-32 and ISIZE.  When the stream produces exactly upto[i] bytes and the
+ *   walk reaches its end, everything cdc_decode_device verifies is verified,
+ *   with its status codes.  (An LZ4 frame is at its end when the end mark
+ *   follows the block that produced byte upto[i] - 1; a gzip member when the
+ *   final block closes without another output byte.)
+ *   A stream that ends before upto[i] bytes is CDC_E_MISMATCH.  upto[i] == 0
+ *   is CDC_OK with nothing of the blob read.  upto[i] >= 2^32 is
+ *   CDC_E_UNSUPPORTED for that blob.
+ *   key != NULL with a compression: every record of the blob is opened (the
+ *   compressed length of a prefix is not known before the walk), so a bad tag
+ *   anywhere is CDC_E_AUTH for any upto[i] > 0.  With CDC_COMPRESS_NONE only
+ *   records 0 .. ceil(upto[i] / 65536) - 1 are opened; a bad tag in a later
+ *   record does not fail the prefix, and the blob may be passed without its
+ *   later records (lens[i] = 60 + 65564 per record kept).
+ * Synchronous on `stream`.  CDC_E_INVALID for a NULL array or device out of
+ * range, before the device is touched. */
+int cdc_decode_prefix_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
+                             const uint64_t *upto, uint32_t n, int compressed, const uint8_t *key, uint8_t *d_out,
+                             uint64_t out_cap, uint64_t *out_offsets, int32_t *status, void *stream);
+
 /* The blob check of snapshot/check.go:83-98 (decode, hash, compare with the
  * index checksum) without the plaintext leaving the device: decodes into
  * d_scratch as cdc_decode_device does (CDC_E_NOSPACE and *needed, when given,
@@ -740,6 +774,77 @@ int cdc_restore_add_packfile_path(cdc_restore *r, const char *path);
 int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
                       cdc_restore_stats *stats);
 void cdc_restore_free(cdc_restore *r);
+
+/* Byte ranges of files: the reader behind `plakar cat`, `plakar mount`,
+ * `plakar exec` and the HTTP API's file download (VFilep.Read and Seek,
+ * snapshot/vfs/vfilep.go:58-122, 168-197), which fetches and decodes a whole
+ * chunk again for every Read.  Here a batch of ranges decodes each blob it
+ * touches once, and only as far as its last byte asked for
+ * (cdc_decode_prefix_device), so a 4-KiB page costs about 4 KiB of decode
+ * chain, not its chunk and not its file.
+ * A range is (files[file], offset, length) and means the file's bytes
+ * [offset, min(offset + length, size)).  offset == size or length == 0 is an
+ * empty range that succeeds; offset > size is CDC_E_INVALID for that range
+ * alone (Seek's rule), and so is a file index out of bounds.  Overlapping
+ * ranges, the same range twice and ranges in any file order are legal. */
+typedef struct cdc_read_range {
+    uint32_t file;      /* index into files */
+    uint32_t reserved;  /* 0 */
+    uint64_t offset, length;
+} cdc_read_range;
+typedef struct cdc_read_result {
+    int index;                 /* position in ranges */
+    int status;                /* CDC_OK, CDC_E_INVALID, CDC_E_NOTFOUND, CDC_E_IO, CDC_E_MISMATCH or a blob's Decode error */
+    uint32_t piece, pieces;    /* this call's piece of the range (pieces == 1: all of it) */
+    const uint8_t *data;       /* status == CDC_OK: range bytes [data_offset, + data_len), valid during the call only */
+    uint64_t data_offset, data_len;
+    uint64_t length;           /* the bytes the whole range delivers: min(length, size - offset) */
+} cdc_read_result;
+/* A new struct with its size in front (set struct_size = sizeof before the
+ * call; the library fills that many bytes): cdc_restore_stats has no such
+ * field and cannot grow. */
+typedef struct cdc_read_stats {
+    uint32_t struct_size, reserved;
+    uint64_t ranges, failed_ranges;
+    uint64_t bytes;            /* output bytes: the ranges' lengths, summed */
+    uint64_t segments;         /* (range, chunk) overlaps */
+    uint64_t batches;
+    uint64_t distinct_blobs;   /* distinct blobs touched by the run */
+    uint64_t whole_blobs;      /* per batch, the blobs decoded to their recorded length ... */
+    uint64_t prefix_blobs;     /* ... and those decoded only so far */
+    uint64_t verified_blobs;   /* whole blobs whose SHA-256 was compared (verify) */
+    uint64_t encoded_bytes;    /* gathered and uploaded */
+    uint64_t decoded_bytes;    /* the sum of upto: what the decode chains produced */
+    uint64_t skipped_bytes;    /* the sum of recorded length - upto: what they did not have to */
+    double read_s, h2d_s, decode_s, verify_s, assemble_s, d2h_s;  /* wall time of each stage, summed */
+    double wall_s;
+} cdc_read_stats;
+typedef void (*cdc_read_range_fn)(void *ctx, const cdc_read_result *r);
+/* Runs on a restore context: its packfiles, locator, key, compression,
+ * streams and buffers (files[i].path is ignored; one run of either kind at a
+ * time per context).  The ranges are laid into batches in the caller's order
+ * (batch_bytes bounds both a batch's output and the bytes it decodes; a larger
+ * range goes in pieces cut on chunk boundaries).  Per batch: reader threads
+ * gather the distinct encoded blobs (whole, except that without compression
+ * only the header and the records that hold the prefix are read), one
+ * host-to-device copy, one cdc_decode_prefix_device with upto = the largest
+ * end offset any range of the batch has inside the blob, with verify SHA-256
+ * and compare for exactly the blobs decoded to their recorded length (a
+ * prefix cannot be hashed: its integrity is what GCM gives), one
+ * cdc_assemble_device into the output image, one device-to-host copy, then
+ * on_range once per range piece, in the caller's order, from one library
+ * thread at a time.
+ * Failures are per range and the run goes on: a checksum in no packfile
+ * (CDC_E_NOTFOUND), a blob that cannot be read (CDC_E_IO), fails Decode, ends
+ * before the bytes asked for or differs from its checksum (CDC_E_MISMATCH)
+ * fails every range that touches that blob and no other range, not even of
+ * the same file.  A range's last call carries its final status; a caller that
+ * was handed earlier pieces of a range that then fails drops them.
+ * CDC_E_INVALID before the device is touched: NULL r, nfiles < 0 or nranges <
+ * 0, NULL arrays, a file without its chunk arrays, stats->struct_size < 8.
+ * Returns CDC_OK, or the run's own first failure (a device error). */
+int cdc_restore_ranges(cdc_restore *r, const cdc_restore_file *files, int nfiles, const cdc_read_range *ranges,
+                       int nranges, cdc_read_range_fn on_range, void *ctx, cdc_read_stats *stats);
 
 /* ---- check: a snapshot's chunks and object checksums -------------------------------
  * `plakar check` (snapshot/check.go:56-113) and `plakar checksum`

@@ -157,6 +157,26 @@ class cdc_restore_stats(ctypes.Structure):
                                                "write_s", "wall_s")]
 
 
+class cdc_read_range(ctypes.Structure):
+    _fields_ = [("file", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("offset", ctypes.c_uint64),
+                ("length", ctypes.c_uint64)]
+
+
+class cdc_read_result(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_int), ("status", ctypes.c_int), ("piece", ctypes.c_uint32),
+                ("pieces", ctypes.c_uint32), ("data", ctypes.POINTER(ctypes.c_uint8)),
+                ("data_offset", ctypes.c_uint64), ("data_len", ctypes.c_uint64), ("length", ctypes.c_uint64)]
+
+
+class cdc_read_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("ranges", "failed_ranges", "bytes", "segments", "batches",
+                                               "distinct_blobs", "whole_blobs", "prefix_blobs", "verified_blobs",
+                                               "encoded_bytes", "decoded_bytes", "skipped_bytes")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "assemble_s", "d2h_s",
+                                               "wall_s")]
+
+
 class cdc_check_opts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
                 ("fast", ctypes.c_int), ("threads", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
@@ -220,6 +240,7 @@ CDC_ARCHIVE_FILE, CDC_ARCHIVE_DIR = 0, 1
 ARCHIVE_DATA_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 ARCHIVE_ENTRY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)
 RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_restore_result))
+READ_RANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_read_result))
 CHECK_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_check_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
@@ -339,6 +360,10 @@ SIGNATURES = {
     "cdc_decode_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
                                          ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32), ctypes.c_void_p]),
+    "cdc_decode_prefix_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64),
+                                                _P(ctypes.c_uint64), _P(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_int,
+                                                ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                                _P(ctypes.c_int32), ctypes.c_void_p]),
     "cdc_check_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                         ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_int32),
@@ -365,6 +390,8 @@ SIGNATURES = {
     "cdc_restore_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "cdc_restore_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, RESTORE_FILE_FN,
                                          ctypes.c_void_p, _P(cdc_restore_stats)]),
+    "cdc_restore_ranges": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, _P(cdc_read_range),
+                                          ctypes.c_int, READ_RANGE_FN, ctypes.c_void_p, _P(cdc_read_stats)]),
     "cdc_restore_free": (None, [ctypes.c_void_p]),
     "cdc_object_digests_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
                                                  _P(ctypes.c_uint64), ctypes.c_uint64, _P(ctypes.c_uint64),

@@ -21,7 +21,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in ("cdc_kernels.hip", "cdc_diges
                                                     "cdc_restore.hip", "cdc_restore.cpp", "cdc_transcode.hip",
                                                     "cdc_archive.cpp", "cdc_check.cpp")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("cdc_internal.h", "cdc_hostmem.h", "cdc_crypto_dev.h", "lz4_walk.h",
-                                                   "inflate_walk.h", "deflate_enc.h", "cdc_encode_dev.h", "restore_plan.h",
+                                                   "inflate_walk.h", "deflate_enc.h", "cdc_encode_dev.h", "restore_plan.h", "read_plan.h",
                                                    "transcode_plan.h", "archive_plan.h", "zip_plan.h", "cdc_locator.h", "check_plan.h",
                                                    "sha_blocks.h", "hybrid_model.h")] + \
           [os.path.join(ROOT, "include", "plakar_cdc.h")]

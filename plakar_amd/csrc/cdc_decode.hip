@@ -38,6 +38,16 @@
 //                 the claim: inflate_walk.h bounds every literal and match),
 //                 then CRC-32 and ISIZE against the output.  Every failure
 //                 here is late (kFlagLate): k_dec_compact closes the gap
+// cdc_decode_prefix_device (the first upto[i] bytes of blob i; the sizes are an
+// input, so nothing is sized, planned on the device or compacted):
+//   k_lz4_prefix  one wave per blob: k_lz4_emit's walk in the walker's stop
+//                 mode, the sequence that crosses upto cut to the byte; block
+//                 checksums of the blocks walked to their end, and the frame's
+//                 end (content size and checksum) only when the walk gets there
+//   k_gz_prefix   one wave per blob: k_gz_emit's walk in the stop mode; CRC-32
+//                 and ISIZE only when the walk reaches the final block's end
+//   k_prefix_copy not compressed: the first upto bytes, of the blob or of the
+//                 records opened for it (k_rec_open into a frame slot)
 //
 // No block table is kept: both LZ4 passes walk the frame from its header, so
 // a frame of very many short blocks needs no memory of its own (it only runs
@@ -700,6 +710,158 @@ __global__ __launch_bounds__(kGzWaves * 64) void k_gz_emit(const DBatch B)
 }
 
 // ---------------------------------------------------------------------------
+// g. Prefix Decode (cdc_decode_prefix_device): the first upto[b] plaintext
+// bytes of blob b, one wave per blob, no sizing pass.  B.dsize holds upto and
+// B.out_off the host's exclusive sum of it, both staged before the launch.
+// The walkers run in their stop mode (lz4w::next_seq_stop, infw::
+// inflate_body_stop), which cuts the sequence that crosses upto to the byte,
+// so blob b writes B.out + [out_off[b], out_off[b] + upto[b]) and nothing
+// else.  Only a walk that reaches the stream's end verifies what lies there.
+// ---------------------------------------------------------------------------
+__device__ int64_t wave_block_prefix(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t omax, uint32_t stop,
+                                     uint32_t lane, bool &stopped)
+{
+    WaveRd rd{src, n, lane, n, 0u};
+    uint32_t ip = 0, opos = 0, published = 0;
+    for (;;) {
+        lz4w::Seq s;
+        const int r = lz4w::next_seq_stop(rd, n, ip, opos, omax, stop, s);
+        if (r < 0) return -1;
+        if (s.lit_len) copy_exact(dst + opos, src + s.lit_src, s.lit_len, lane, 64);
+        opos += s.lit_len;
+        if (r == lz4w::kEnd) return int64_t(opos);
+        if (s.mlen) {
+            if (opos - s.off + min(s.off, s.mlen) > published) {
+                wave_publish();
+                published = opos;
+            }
+            if (s.off >= s.mlen) {
+                copy_exact(dst + opos, dst + opos - s.off, s.mlen, lane, 64);
+            } else {
+                for (uint32_t i = lane; i < s.mlen; i += 64) dst[opos + i] = dst[lz4w::match_src(opos, s.off, s.mlen, i)];
+            }
+        }
+        opos += s.mlen;
+        if (r == lz4w::kStop) {
+            stopped = true;
+            return int64_t(opos);
+        }
+    }
+}
+
+// The first upto (> 0) bytes of the frame f[0, flen) into dst[0, upto).
+__device__ int32_t wave_frame_prefix(const uint8_t *f, uint64_t flen, uint8_t *dst, uint64_t upto, uint32_t lane)
+{
+    if (flen == 0) return CDC_E_MISMATCH;  // the empty blob ends before any byte
+    FrameHdr F;
+    const int32_t st = frame_header(f, flen, F);
+    if (st != CDC_OK) return st;
+    uint64_t pos = F.hlen, opos = 0;
+    for (;;) {
+        // Everything wanted is out at a block's edge: only an end mark right
+        // here makes this the whole stream, anything else is left unread.
+        if (opos == upto && (flen - pos < 4 || ld32u(f + pos) != 0)) return CDC_OK;
+        if (flen - pos < 4) return CDC_E_CORRUPT;
+        const uint32_t word = ld32u(f + pos);
+        pos += 4;
+        if (word == 0) break;
+        const uint32_t size = word & 0x7FFFFFFFu;
+        if (size == 0 || size > F.bmax || flen - pos < size) return CDC_E_CORRUPT;
+        const uint32_t stop = uint32_t(min<uint64_t>(F.bmax, upto - opos));
+        bool stopped = false;
+        int64_t d;
+        if (word >> 31) {  // stored
+            d = min(size, stop);
+            copy_exact(dst + opos, f + pos, uint64_t(d), lane, 64);
+            stopped = size > stop;
+        } else {
+            d = wave_block_prefix(f + pos, size, dst + opos, F.bmax, stop, lane, stopped);
+            if (d < 0) return CDC_E_CORRUPT;
+        }
+        opos += uint64_t(d);
+        if (stopped) return CDC_OK;
+        if (F.bchk && (flen - pos - size < 4 || wave_xxh32(f + pos, size, lane) != ld32u(f + pos + size)))
+            return CDC_E_CORRUPT;
+        pos += uint64_t(size) + (F.bchk ? 4 : 0);
+    }
+    // the stream's end: what cdc_decode_device verifies there
+    uint32_t want = 0;
+    if (F.cchk) {
+        if (flen - pos < 4) return CDC_E_CORRUPT;
+        want = ld32u(f + pos);
+        pos += 4;
+    }
+    if (pos != flen) return CDC_E_CORRUPT;
+    if (F.csize && opos != F.content) return CDC_E_CORRUPT;
+    if (F.cchk) {
+        wave_publish();
+        if (wave_xxh32(dst, opos, lane) != want) return CDC_E_CORRUPT;
+    }
+    return opos == upto ? CDC_OK : CDC_E_MISMATCH;  // it ended before upto
+}
+
+__global__ __launch_bounds__(kFrameWaves * 64) void k_lz4_prefix(const DBatch B)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t b = blockIdx.x * kFrameWaves + (threadIdx.x >> 6);
+    if (b >= B.n || B.status[b]) return;
+    const DBlob D = B.blobs[b];
+    const int32_t st = wave_frame_prefix(stream_ptr(B, D), D.flen, B.out + B.out_off[b], B.dsize[b], lane);
+    if (st != CDC_OK && lane == 0) B.status[b] = st;
+}
+
+// Five waves per SIMD, as k_gz_emit has them: the stop tests cost nine more
+// registers than its 96 unless the compiler is held to that budget (no spill).
+__global__ __launch_bounds__(kGzWaves * 64) __attribute__((amdgpu_waves_per_eu(5))) void k_gz_prefix(const DBatch B)
+{
+    __shared__ infw::Tables s_fixed;
+    __shared__ infw::Tables s_dyn[kGzWaves];
+    __shared__ uint32_t s_crc[256];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    WavePar par{lane};
+    if (wv == 0) infw::build_fixed(par, s_fixed);
+    for (uint32_t i = threadIdx.x; i < 256; i += kGzWaves * 64) s_crc[i] = infw::crc_bits(0, i);
+    __syncthreads();
+    const uint32_t b = blockIdx.x * kGzWaves + wv;
+    if (b >= B.n || B.status[b]) return;
+    const DBlob D = B.blobs[b];
+    const uint32_t upto = uint32_t(B.dsize[b]);  // 0 < upto < 2^32: the host checked
+    int32_t res = CDC_OK;
+    if (D.flen == 0) {
+        res = CDC_E_MISMATCH;  // the empty blob ends before any byte
+    } else if (D.flen > infw::kMaxStream) {
+        res = CDC_E_UNSUPPORTED;
+    } else {
+        const uint32_t n = uint32_t(D.flen);
+        const uint8_t *f = stream_ptr(B, D);
+        uint8_t *dst = B.out + B.out_off[b];
+        WaveRd rd{f, n, lane, n, 0u};
+        uint32_t hlen = 0, opos = 0, end = 0;
+        bool stopped = false;
+        int st = infw::member_header(rd, n, hlen);
+        if (st == infw::kOk) {
+            GzSink sink{dst, f, lane, 0u, 0u, 0u, 0u};
+            st = infw::inflate_body_stop(rd, n, hlen, sink, upto, s_dyn[wv], s_fixed, par, opos, end, stopped);
+        }
+        if (st == infw::kOk && !stopped) {  // the stream's end: the trailer against what is out
+            wave_publish();
+            st = infw::member_trailer(rd, n, end, opos, wave_crc32(dst, opos, lane, s_crc));
+        }
+        res = gz_status(st);
+        if (res == CDC_OK && opos != upto) res = CDC_E_MISMATCH;  // it ended before upto
+    }
+    if (res != CDC_OK && lane == 0) B.status[b] = res;
+}
+
+// Not compressed: the first upto bytes of the blob, or of its opened records.
+__global__ __launch_bounds__(256) void k_prefix_copy(const DBatch B)
+{
+    const uint32_t b = blockIdx.x;
+    if (B.status[b]) return;
+    copy_exact(B.out + B.out_off[b], stream_ptr(B, B.blobs[b]), B.dsize[b], threadIdx.x, blockDim.x);
+}
+
+// ---------------------------------------------------------------------------
 // The plan: out_off = exclusive scan of the sizes of the blobs that decoded.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPlanThreads = 1024;
@@ -813,8 +975,10 @@ static bool bad_args(int device, const void *d_in, const uint64_t *offsets, cons
 // CDC_E_MISMATCH where the SHA-256 differs from checksums[32 i].  The plaintext
 // is only read.  Synchronous on `stream`.
 static int check_decoded(int device, const uint8_t *d_scratch, const uint64_t *oo, uint32_t n,
-                         const uint8_t *checksums, int32_t *status, void *stream)
+                         const uint8_t *checksums, int32_t *status, void *stream, const uint8_t *only = nullptr)
 {
+    // only != NULL: blob b is hashed and compared where only[b] != 0, and left alone elsewhere
+    auto checked = [&](uint32_t b) { return status[b] == CDC_OK && (!only || only[b]); };
     int st;
     // SHA-256 of every blob on the device (k_chunk_digest hashes an empty chunk
     // to SHA-256("")); a blob that did not decode is an empty cut whose row is
@@ -830,7 +994,7 @@ static int check_decoded(int device, const uint8_t *d_scratch, const uint64_t *o
     uint8_t *const ws = C.ws.as<uint8_t>(), *const hp = C.stage.as<uint8_t>();
     cdc_cut *cuts = reinterpret_cast<cdc_cut *>(hp + o_cuts);
     for (uint32_t b = 0; b < n; ++b) {
-        const uint64_t len = status[b] == CDC_OK ? oo[b + 1] - oo[b] : 0;
+        const uint64_t len = checked(b) ? oo[b + 1] - oo[b] : 0;
         cuts[b] = cdc_cut{len ? oo[b] : 0, uint32_t(len), 0};
     }
     std::memcpy(hp + o_want, checksums, m * 32);
@@ -848,7 +1012,7 @@ static int check_decoded(int device, const uint8_t *d_scratch, const uint64_t *o
         hipStreamSynchronize(s) != hipSuccess)
         return CDC_E_DEVICE;
     for (uint32_t b = 0; b < n; ++b)
-        if (status[b] == CDC_OK && diff[b]) status[b] = CDC_E_MISMATCH;
+        if (checked(b) && diff[b]) status[b] = CDC_E_MISMATCH;
     return CDC_OK;
 }
 
@@ -876,9 +1040,140 @@ static BlobPlan plan_blob(uint64_t len, bool encrypt, int compressed)
     return P;
 }
 
+// The host plan of a prefix: what cdc_decode_device plans from the lengths,
+// narrowed by upto.  A blob with upto == 0 is kSkip (nothing of it is read;
+// reported as CDC_OK); without compression only the records that hold the
+// prefix are opened, and they land in a frame slot that k_prefix_copy reads.
+constexpr int32_t kSkip = 1;
+struct PrefixPlan {
+    uint64_t nr, flen, slot;
+    int32_t status;
+};
+static PrefixPlan plan_prefix(uint64_t len, uint64_t upto, bool encrypt, int compressed)
+{
+    if (upto == 0) return PrefixPlan{0, 0, 0, kSkip};
+    if (upto > 0xFFFFFFFFull) return PrefixPlan{0, 0, 0, CDC_E_UNSUPPORTED};  // a blob is a cdc_cut: 32-bit length
+    const BlobPlan P = plan_blob(len, encrypt, compressed);
+    if (P.status != CDC_OK) return PrefixPlan{0, 0, 0, P.status};
+    if (compressed) return PrefixPlan{P.nr, P.flen, P.slot, CDC_OK};
+    if (upto > P.flen) return PrefixPlan{0, 0, 0, CDC_E_MISMATCH};
+    if (!encrypt) return PrefixPlan{0, P.flen, 0, CDC_OK};
+    const uint64_t nr = (upto + kPiece - 1) / kPiece;
+    return PrefixPlan{nr, P.flen, cdc::align_up(std::min<uint64_t>(P.flen, nr * kPiece), 16), CDC_OK};
+}
+
 }  // namespace dec
 
 using namespace dec;
+
+extern "C" int cdc_decode_prefix_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
+                                        const uint64_t *upto, uint32_t n, int compressed, const uint8_t *key,
+                                        uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets, int32_t *status,
+                                        void *stream)
+{
+    if (bad_args(device, d_in, offsets, lens, n, status) || (n && !upto) || !out_offsets || (!d_out && out_cap))
+        return CDC_E_INVALID;
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        out_offsets[b] = total;
+        if (upto[b] > UINT64_MAX - total) return CDC_E_INVALID;
+        total += upto[b];
+    }
+    out_offsets[n] = total;
+    if (total > out_cap) return CDC_E_NOSPACE;
+    const bool encrypt = key != nullptr;
+    uint64_t slot = 0, nrecs = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        const PrefixPlan P = plan_prefix(lens[b], upto[b], encrypt, compressed);
+        status[b] = P.status == kSkip ? CDC_OK : P.status;
+        nrecs += P.nr;
+        slot += P.slot;
+    }
+    if (total == 0) return CDC_OK;  // nothing is wanted: nothing is read
+    if (nrecs > 0x7FFFFFFFull) return CDC_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
+    int st = cdc::upload_aes_tables(g_tab, g_te0, g_sbox);
+    if (st != CDC_OK) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t nb = n;
+    cdc::Carver cv(16);
+    // the staged prefix (blobs, status, key, upto, offsets), then what only the device touches
+    const size_t o_blobs = cv.take(nb * sizeof(DBlob)), o_status = cv.take(nb * 4), o_key = cv.take(32),
+                 o_dsize = cv.take(nb * 8), o_oo = cv.take((nb + 1) * 8), h_prefix = cv.bytes();
+    const size_t o_keys = cv.take(encrypt ? nb * sizeof(BlobKey) : 0), o_flags = cv.take(16),
+                 o_frames = cv.take(encrypt ? slot : 0);
+    WsCache &C = g_ws[device];
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.ws.reserve(cv.bytes()) || !C.stage.reserve(h_prefix)) return CDC_E_NOMEM;
+    const int cus = cdc::device_cus(device);
+    uint8_t *const ws = C.ws.as<uint8_t>(), *const hp = C.stage.as<uint8_t>();
+    {
+        DBlob *blobs = reinterpret_cast<DBlob *>(hp + o_blobs);
+        int32_t *hst = reinterpret_cast<int32_t *>(hp + o_status);
+        uint64_t sl = 0;
+        uint32_t rec = 0;
+        for (uint32_t b = 0; b < n; ++b) {
+            const PrefixPlan P = plan_prefix(lens[b], upto[b], encrypt, compressed);
+            DBlob D{};
+            D.src = offsets[b];
+            D.len = lens[b];
+            D.flen = P.flen;
+            D.rec0 = rec;
+            D.nrec = uint32_t(P.nr);
+            D.slot = sl;
+            hst[b] = P.status;
+            sl += P.slot;
+            rec += D.nrec;
+            blobs[b] = D;
+        }
+        std::memcpy(hp + o_dsize, upto, nb * 8);
+        std::memcpy(hp + o_oo, out_offsets, (nb + 1) * 8);
+        if (encrypt) std::memcpy(hp + o_key, key, 32);
+    }
+    DBatch B{};
+    B.in = static_cast<const uint8_t *>(d_in);
+    B.n = n;
+    B.compressed = compressed == CDC_COMPRESS_GZIP ? 2u : compressed ? 1u : 0u;
+    B.encrypted = encrypt ? 1u : 0u;
+    B.nrecs = uint32_t(nrecs);
+    B.blobs = reinterpret_cast<const DBlob *>(ws + o_blobs);
+    B.key = ws + o_key;
+    B.frames = ws + o_frames;
+    B.out = d_out;
+    B.out_cap = out_cap;
+    B.keys = reinterpret_cast<BlobKey *>(ws + o_keys);
+    B.status = reinterpret_cast<int32_t *>(ws + o_status);
+    B.dsize = reinterpret_cast<uint64_t *>(ws + o_dsize);
+    B.out_off = reinterpret_cast<uint64_t *>(ws + o_oo);
+    B.flags = reinterpret_cast<uint32_t *>(ws + o_flags);
+    bool ok = hipMemcpyAsync(ws, hp, h_prefix, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemsetAsync(ws + o_flags, 0, 16, s) == hipSuccess;
+    if (ok) {
+        if (encrypt) {
+            const uint32_t open_wgs = uint32_t(std::min<uint64_t>((nrecs + kGcmWaves - 1) / kGcmWaves, uint64_t(cus)));
+            hipLaunchKernelGGL(k_dec_keys, dim3((n + kKeyThreads - 1) / kKeyThreads), dim3(kKeyThreads), 0, s, B);
+            hipLaunchKernelGGL(k_dec_pows, dim3((n + kPowWaves - 1) / kPowWaves), dim3(kPowWaves * 64), 0, s, B);
+            if (nrecs)
+                hipLaunchKernelGGL(k_rec_open, dim3(open_wgs), dim3(kGcmWaves * 64), 0, s, B, kOpenHash | kOpenCtr);
+        }
+        if (B.compressed == 2u)
+            hipLaunchKernelGGL(k_gz_prefix, dim3((n + kGzWaves - 1) / kGzWaves), dim3(kGzWaves * 64), 0, s, B);
+        else if (B.compressed)
+            hipLaunchKernelGGL(k_lz4_prefix, dim3((n + kFrameWaves - 1) / kFrameWaves), dim3(kFrameWaves * 64), 0, s, B);
+        else
+            hipLaunchKernelGGL(k_prefix_copy, dim3(n), dim3(256), 0, s, B);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    // the repository key does not outlive the call (see cdc_decode_device)
+    if (encrypt) ok = ok && hipMemsetAsync(ws + o_key, 0, 32, s) == hipSuccess;
+    ok = ok && hipMemcpyAsync(status, ws + o_status, nb * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+         hipStreamSynchronize(s) == hipSuccess;
+    if (encrypt) std::memset(hp + o_key, 0, 32);
+    if (!ok) return CDC_E_DEVICE;
+    for (uint32_t b = 0; b < n; ++b)
+        if (status[b] == kSkip) status[b] = CDC_OK;
+    return CDC_OK;
+}
 
 extern "C" int cdc_decode_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
                                  uint32_t n, int compressed, const uint8_t *key, uint8_t *d_out, uint64_t out_cap,
@@ -1029,6 +1324,27 @@ int cdc::decode_checked(int device, const void *d_in, const uint64_t *offsets, c
     if (decode_s) *decode_s += std::chrono::duration<double>(t1 - t0).count();
     if (st != CDC_OK || !checksums || n == 0) return st;
     st = check_decoded(device, d_out, out_offsets, n, checksums, status, stream);
+    if (verify_s) *verify_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return st;
+}
+
+// cdc_restore.cpp's seam for ranged reads: prefix Decode and, with checksums,
+// the check of the blobs that were decoded whole.
+int cdc::decode_prefix_checked(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
+                               const uint64_t *upto, uint32_t n, int compressed, const uint8_t *key,
+                               const uint8_t *checksums, const uint8_t *whole, uint8_t *d_out, uint64_t out_cap,
+                               uint64_t *out_offsets, int32_t *status, void *stream, double *decode_s, double *verify_s)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    int st = cdc_decode_prefix_device(device, d_in, offsets, lens, upto, n, compressed, key, d_out, out_cap, out_offsets,
+                                      status, stream);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (decode_s) *decode_s += std::chrono::duration<double>(t1 - t0).count();
+    if (st != CDC_OK || !checksums || !whole || n == 0) return st;
+    bool any = false;
+    for (uint32_t b = 0; b < n; ++b) any = any || (whole[b] && status[b] == CDC_OK);
+    if (!any) return st;
+    st = check_decoded(device, d_out, out_offsets, n, checksums, status, stream, whole);
     if (verify_s) *verify_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     return st;
 }

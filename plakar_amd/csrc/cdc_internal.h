@@ -245,6 +245,14 @@ int decode_checked(int device, const void *d_in, const uint64_t *offsets, const 
                    int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_out, uint64_t out_cap,
                    uint64_t *out_offsets, int32_t *status, void *stream, double *decode_s, double *verify_s);
 
+// cdc_decode.hip: cdc_decode_prefix_device, then (checksums != NULL) the same
+// hash-and-compare for the blobs with whole[i] != 0 only: a prefix cannot be
+// hashed against the blob's checksum.
+int decode_prefix_checked(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens,
+                          const uint64_t *upto, uint32_t n, int compressed, const uint8_t *key, const uint8_t *checksums,
+                          const uint8_t *whole, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets, int32_t *status,
+                          void *stream, double *decode_s, double *verify_s);
+
 // The compression levels every entry point takes (CDC_LEVEL_*): any other value is CDC_E_INVALID.
 inline bool level_ok(int level) { return level == CDC_LEVEL_FAST || level == CDC_LEVEL_WIDE || level == CDC_LEVEL_BEST; }
 

@@ -42,6 +42,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "read_plan.h"
 #include "restore_plan.h"
 
 namespace {
@@ -481,6 +482,208 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     return X.fail;
 }
 
+// ---- ranged reads -------------------------------------------------------------------
+// cdc_restore_ranges: the batches of read_plan.h one after the other on the
+// calling thread (gather, upload, prefix Decode + check, assemble, download,
+// callbacks), in the context's first input and output slot.
+constexpr uint64_t kGcmHeader = 60, kGcmRecord = 65536 + 28;
+
+static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles, const cdc_read_range *ranges, int nranges,
+                      cdc_read_range_fn on_range, void *ctx, cdc_read_stats *stats)
+{
+    const auto w0 = Clock::now();
+    cdc_read_stats st{};
+    // the locator: every chunk's blob id, or kMissing (its ranges are CDC_E_NOTFOUND)
+    std::vector<std::vector<uint32_t>> fblob((size_t(nfiles)));
+    std::vector<rplan::File> pf;
+    for (int i = 0; i < nfiles; ++i) {
+        const cdc_restore_file &F = files[i];
+        fblob[size_t(i)].resize(size_t(F.nchunks));
+        for (uint64_t c = 0; c < F.nchunks; ++c) {
+            cdc::Sum s;
+            std::memcpy(s.b, F.checksums + 32 * c, 32);
+            const auto it = R->loc.index.find(s);
+            fblob[size_t(i)][size_t(c)] = it == R->loc.index.end() ? rplan::kMissing : it->second;
+        }
+        pf.push_back(rplan::File{F.nchunks, fblob[size_t(i)].data(), F.lengths});
+    }
+    std::vector<rplan::Range> rr;
+    for (int i = 0; i < nranges; ++i) rr.push_back(rplan::Range{ranges[i].file, ranges[i].offset, ranges[i].length});
+    std::vector<rplan::RBatch> batches;
+    std::vector<rplan::RangeInfo> info;
+    rplan::plan_ranges(pf.data(), pf.size(), rr.data(), rr.size(), R->o.batch_bytes, R->o.batch_bytes, batches, info);
+    std::vector<int> rstatus(size_t(nranges), CDC_OK);
+    auto report = [&](int i, uint32_t piece, const uint8_t *data, uint64_t off, uint64_t len) {
+        if (!on_range) return;
+        cdc_read_result r{};
+        r.index = i;
+        r.status = rstatus[size_t(i)];
+        r.piece = piece;
+        r.pieces = std::max<uint32_t>(info[size_t(i)].pieces, 1);
+        r.data = r.status == CDC_OK ? data : nullptr;
+        r.data_offset = off;
+        r.data_len = r.status == CDC_OK ? len : 0;
+        r.length = info[size_t(i)].length;
+        on_range(ctx, &r);
+    };
+    st.ranges = uint64_t(nranges);
+    for (int i = 0; i < nranges; ++i) {
+        rstatus[size_t(i)] = info[size_t(i)].status;
+        if (rstatus[size_t(i)] != CDC_OK) report(i, 0, nullptr, 0, 0);
+    }
+    std::vector<bool> used(R->loc.locs.size(), false);
+    for (const rplan::RBatch &B : batches) {
+        st.bytes += B.out_bytes;
+        st.segments += B.segs.size();
+        st.decoded_bytes += B.scratch_bytes;
+        for (const rplan::RBlob &b : B.blobs) {
+            ++(b.upto == b.len ? st.whole_blobs : st.prefix_blobs);
+            st.skipped_bytes += b.len - b.upto;
+            if (!used[b.id]) {
+                used[b.id] = true;
+                ++st.distinct_blobs;
+            }
+        }
+    }
+    st.batches = batches.size();
+    int fail = CDC_OK;
+    if (!batches.empty() && hipSetDevice(R->device) != hipSuccess) fail = CDC_E_DEVICE;
+    const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
+    InSlot &I = R->in[0];
+    OutSlot &O = R->out[0];
+    std::vector<uint64_t> upto, oo, so, sl, sd;
+    std::vector<int32_t> bst;
+    std::vector<uint8_t> want, whole;
+    size_t done = 0;  // batches whose callbacks were made
+    for (; done < batches.size() && fail == CDC_OK; ++done) {
+        const rplan::RBatch &B = batches[done];
+        const size_t nb = B.blobs.size();
+        // gather: whole blobs, or without compression the header and the records that hold the prefix
+        auto t0 = Clock::now();
+        I.eoff.assign(nb, 0);
+        I.elen.assign(nb, 0);
+        I.pre.assign(nb, CDC_OK);
+        uint64_t total = 0;
+        std::unordered_map<uint32_t, int> fds;
+        for (size_t b = 0; b < nb; ++b) {
+            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
+            uint64_t need = L.length;
+            if (R->o.compress == CDC_COMPRESS_NONE)
+                need = std::min<uint64_t>(need, key ? kGcmHeader + (B.blobs[b].upto + 65535) / 65536 * kGcmRecord
+                                                    : B.blobs[b].upto);
+            I.eoff[b] = total;
+            I.elen[b] = need;
+            total += need;
+            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
+            if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
+        }
+        const bool room = I.h.reserve(total) && I.d.reserve(total);
+        if (room) {
+            uint8_t *const h = I.h.as<uint8_t>();
+            parallel_for(R->o.writers, nb, [&](size_t b) {
+                const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
+                const cdc::Locator::Pack &P = R->loc.packs[L.pack];
+                if (P.mem) {
+                    std::memcpy(h + I.eoff[b], P.mem + L.offset, I.elen[b]);
+                    return;
+                }
+                const int fd = fds.find(L.pack)->second;
+                if (fd < 0 || !pread_all(fd, h + I.eoff[b], I.elen[b], L.offset)) I.pre[b] = CDC_E_IO;
+            });
+        }
+        for (auto &f : fds)
+            if (f.second >= 0) close(f.second);
+        if (!room) {
+            fail = CDC_E_NOMEM;
+            break;
+        }
+        st.read_s += since(t0);
+        st.encoded_bytes += total;
+        t0 = Clock::now();
+        if (total && (hipMemcpyAsync(I.d.data(), I.h.data(), total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
+                      hipStreamSynchronize(R->stream[0]) != hipSuccess)) {
+            fail = CDC_E_DEVICE;
+            break;
+        }
+        st.h2d_s += since(t0);
+        // prefix Decode into the scratch buffer, the check of the blobs decoded whole
+        if (!R->plain.reserve(B.scratch_bytes) || !O.d.reserve(B.out_bytes) || !O.h.reserve(B.out_bytes)) {
+            fail = CDC_E_NOMEM;
+            break;
+        }
+        upto.assign(nb, 0);
+        whole.assign(nb + 1, 0);
+        oo.assign(nb + 1, 0);
+        bst.assign(std::max<size_t>(nb, 1), CDC_OK);
+        want.resize(nb * 32 + 1);
+        for (size_t b = 0; b < nb; ++b) {
+            upto[b] = B.blobs[b].upto;
+            whole[b] = B.blobs[b].upto == B.blobs[b].len;
+            std::memcpy(&want[b * 32], R->loc.sums[B.blobs[b].id].b, 32);
+            if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
+        }
+        int rc = cdc::decode_prefix_checked(R->device, I.d.data(), I.eoff.data(), I.elen.data(), upto.data(), uint32_t(nb),
+                                            R->o.compress, key, R->o.verify ? want.data() : nullptr, whole.data(),
+                                            R->plain.as<uint8_t>(), B.scratch_bytes, oo.data(), bst.data(), R->stream[1],
+                                            &st.decode_s, &st.verify_s);
+        if (rc != CDC_OK) {
+            fail = rc;
+            break;
+        }
+        for (size_t b = 0; b < nb; ++b) {
+            if (I.pre[b] != CDC_OK) bst[b] = I.pre[b];
+            if (R->o.verify && whole[b] && bst[b] == CDC_OK) ++st.verified_blobs;
+        }
+        // a blob's failure fails every range of the batch that touches it
+        for (const rplan::RPiece &P : B.pieces)
+            for (uint64_t s = P.seg0; s < P.seg0 + P.nsegs; ++s) {
+                const int32_t e = bst[B.segs[size_t(s)].blob];
+                if (e != CDC_OK && rstatus[P.range] == CDC_OK) rstatus[P.range] = e;
+            }
+        t0 = Clock::now();
+        so.clear();
+        sl.clear();
+        sd.clear();
+        for (const rplan::Segment &S : B.segs) {
+            if (bst[S.blob] != CDC_OK) continue;  // its ranges have failed; their bytes are not delivered
+            so.push_back(S.src_off);
+            sl.push_back(S.len);
+            sd.push_back(S.dst_off);
+        }
+        if (!so.empty())
+            rc = cdc_assemble_device(R->device, R->plain.data(), B.scratch_bytes, so.data(), sl.data(), sd.data(), so.size(),
+                                     O.d.data(), B.out_bytes, R->stream[1]);
+        if (rc == CDC_OK && hipStreamSynchronize(R->stream[1]) != hipSuccess) rc = CDC_E_DEVICE;
+        if (rc != CDC_OK) {
+            fail = rc;
+            break;
+        }
+        st.assemble_s += since(t0);
+        t0 = Clock::now();
+        uint8_t *const image = O.h.as<uint8_t>();
+        if (B.out_bytes && (hipMemcpyAsync(image, O.d.data(), B.out_bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
+                            hipStreamSynchronize(R->stream[2]) != hipSuccess)) {
+            fail = CDC_E_DEVICE;
+            break;
+        }
+        st.d2h_s += since(t0);
+        for (const rplan::RPiece &P : B.pieces) report(int(P.range), P.piece, image + P.dst_off, P.range_off, P.len);
+    }
+    // a run that broke off: the pieces it did not deliver fail with its status
+    for (; done < batches.size(); ++done)
+        for (const rplan::RPiece &P : batches[done].pieces) {
+            rstatus[P.range] = fail;
+            report(int(P.range), P.piece, nullptr, P.range_off, 0);
+        }
+    for (int i = 0; i < nranges; ++i) st.failed_ranges += rstatus[size_t(i)] != CDC_OK;
+    st.wall_s = since(w0);
+    if (stats) {
+        st.struct_size = uint32_t(std::min<size_t>(stats->struct_size, sizeof(st)));
+        std::memcpy(stats, &st, st.struct_size);
+    }
+    return fail;
+}
+
 }  // namespace
 
 extern "C" {
@@ -563,6 +766,21 @@ int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_
     std::lock_guard<std::mutex> lk(r->run_mu);
     try {
         return run_files(r, files, n, on_file, ctx, stats);
+    } catch (const std::bad_alloc &) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_restore_ranges(cdc_restore *r, const cdc_restore_file *files, int nfiles, const cdc_read_range *ranges,
+                       int nranges, cdc_read_range_fn on_range, void *ctx, cdc_read_stats *stats)
+{
+    if (!r || nfiles < 0 || nranges < 0 || (nfiles && !files) || (nranges && !ranges) || (stats && stats->struct_size < 8))
+        return CDC_E_INVALID;
+    for (int i = 0; i < nfiles; ++i)
+        if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(r->run_mu);
+    try {
+        return run_ranges(r, files, nfiles, ranges, nranges, on_range, ctx, stats);
     } catch (const std::bad_alloc &) {
         return CDC_E_NOMEM;
     }

@@ -334,43 +334,72 @@ INFW_HD bool read_dynamic(Bits<Rd> &B, Tables &T, Par &par)
 // bytes produced (<= omax) and `end` the index of the byte after the last
 // block, or kCorrupt.  Every sink call lies inside [0, omax) and its sources
 // inside the input or the output before it.
-template <class Rd, class Sink, class Par>
-INFW_HD int inflate_body(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t omax, Tables &dyn, const Tables &fixed,
-                         Par &par, uint32_t &opos, uint32_t &end)
+//
+// kStop is the stop mode (prefix Decode): omax is then the number of bytes
+// wanted, and output that would pass it is no fault.  The literal, match or
+// stored block that crosses the cut is cut to the byte (a stored block's bytes
+// past the cut need not lie inside the input), the sink is flushed, `stopped`
+// is set and the walk ends with kOk; `end` is then not set.  Once omax bytes
+// are out, nothing read after them can fail the walk: a block header, a code
+// set or a code that is not well formed ends it the same way, stopped.  Only a
+// walk that reaches the end of the final block with stopped == false has seen
+// the whole stream, judged as the full walk judges it.
+template <bool kStop, class Rd, class Sink, class Par>
+INFW_HD int inflate_walk(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t omax, Tables &dyn, const Tables &fixed,
+                         Par &par, uint32_t &opos, uint32_t &end, bool &stopped)
 {
     Bits<Rd> B{rd, n, ip0, 0, 0};
     opos = 0;
+    stopped = false;
+    // A fault: kCorrupt, or in the stop mode with everything wanted out, the end of the walk.
+#define INFW_FAIL()                        \
+    do {                                   \
+        if (kStop && opos >= omax) {       \
+            sink.flush();                  \
+            stopped = true;                \
+            return kOk;                    \
+        }                                  \
+        return kCorrupt;                   \
+    } while (0)
     for (;;) {
         uint32_t hdr;
         B.refill();
-        if (!B.take(3, hdr)) return kCorrupt;
+        if (!B.take(3, hdr)) INFW_FAIL();
         const uint32_t btype = hdr >> 1;
-        if (btype == 3) return kCorrupt;
+        if (btype == 3) INFW_FAIL();
         if (btype == 0) {
             B.drop(B.cnt & 7u);
             const uint32_t at = B.align();
-            if (n - at < 4) return kCorrupt;
-            const uint32_t len = rd(at) | rd(at + 1) << 8, nlen = rd(at + 2) | rd(at + 3) << 8;
-            if ((len ^ nlen) != 0xFFFFu) return kCorrupt;
-            if (len > n - (at + 4) || len > omax - opos) return kCorrupt;
+            if (n - at < 4) INFW_FAIL();
+            uint32_t len = rd(at) | rd(at + 1) << 8;
+            const uint32_t nlen = rd(at + 2) | rd(at + 3) << 8;
+            if ((len ^ nlen) != 0xFFFFu) INFW_FAIL();
+            const bool cut = kStop && len > omax - opos;
+            if (cut) len = omax - opos;
+            if (len > n - (at + 4) || len > omax - opos) INFW_FAIL();
             if (len) sink.stored(opos, at + 4, len);
             opos += len;
+            if (cut) {
+                sink.flush();
+                stopped = true;
+                return kOk;
+            }
             B.ip = at + 4 + len;
         } else {
-            if (btype == 2 && !read_dynamic(B, dyn, par)) return kCorrupt;
+            if (btype == 2 && !read_dynamic(B, dyn, par)) INFW_FAIL();
             const Tables &T = btype == 2 ? dyn : fixed;
             for (;;) {
                 B.refill();  // 15 + 5 + 15 + 13 bits at the most until the next refill
                 const int s = decode_sym(B, T.lit, kLitBits, T.litcnt, T.litsym);
-                if (s < 0) return kCorrupt;
+                if (s < 0) INFW_FAIL();
                 if (s < 256) {
-                    if (opos >= omax) return kCorrupt;
+                    if (opos >= omax) INFW_FAIL();
                     sink.lit(opos, uint32_t(s));
                     ++opos;
                     continue;
                 }
                 if (s == 256) break;
-                if (s > 285) return kCorrupt;
+                if (s > 285) INFW_FAIL();
                 const uint32_t c = uint32_t(s) - 257;
                 uint32_t len, x;
                 if (c < 8) {
@@ -379,20 +408,29 @@ INFW_HD int inflate_body(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t 
                     len = 258;
                 } else {
                     const uint32_t e = (c >> 2) - 1;
-                    if (!B.take(e, x)) return kCorrupt;
+                    if (!B.take(e, x)) INFW_FAIL();
                     len = 3 + ((4 + (c & 3u)) << e) + x;
                 }
                 const int d = decode_sym(B, T.dist, kDistBits, T.distcnt, T.distsym);
-                if (d < 0 || d > 29) return kCorrupt;
+                if (d < 0 || d > 29) INFW_FAIL();
                 uint32_t dist;
                 if (d < 4) {
                     dist = 1 + uint32_t(d);
                 } else {
                     const uint32_t e = (uint32_t(d) >> 1) - 1;
-                    if (!B.take(e, x)) return kCorrupt;
+                    if (!B.take(e, x)) INFW_FAIL();
                     dist = 1 + ((2 + (uint32_t(d) & 1u)) << e) + x;
                 }
-                if (dist > opos || len > omax - opos) return kCorrupt;
+                if (dist > opos) INFW_FAIL();
+                if (len > omax - opos) {
+                    if (!kStop) return kCorrupt;
+                    len = omax - opos;
+                    if (len) sink.match(opos, dist, len);
+                    opos += len;
+                    sink.flush();
+                    stopped = true;
+                    return kOk;
+                }
                 sink.match(opos, dist, len);
                 opos += len;
             }
@@ -400,9 +438,26 @@ INFW_HD int inflate_body(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t 
         sink.flush();
         if (hdr & 1u) break;
     }
+#undef INFW_FAIL
     B.drop(B.cnt & 7u);
     end = B.align();
     return kOk;
+}
+
+template <class Rd, class Sink, class Par>
+INFW_HD int inflate_body(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t omax, Tables &dyn, const Tables &fixed,
+                         Par &par, uint32_t &opos, uint32_t &end)
+{
+    bool stopped;
+    return inflate_walk<false>(rd, n, ip0, sink, omax, dyn, fixed, par, opos, end, stopped);
+}
+
+// The stop mode of inflate_body: the first `stop` bytes of the stream.
+template <class Rd, class Sink, class Par>
+INFW_HD int inflate_body_stop(Rd &rd, uint32_t n, uint32_t ip0, Sink &sink, uint32_t stop, Tables &dyn,
+                              const Tables &fixed, Par &par, uint32_t &opos, uint32_t &end, bool &stopped)
+{
+    return inflate_walk<true>(rd, n, ip0, sink, stop, dyn, fixed, par, opos, end, stopped);
 }
 
 // ---- the member --------------------------------------------------------------------

@@ -85,6 +85,58 @@ LZ4W_HD int next_seq(Rd &rd, uint32_t n, uint32_t &ip, uint32_t opos, uint32_t o
     return kSeq;
 }
 
+// The stop mode (prefix Decode): next_seq for a caller that wants the block's
+// output only up to `stop` (<= omax).  kStop is a fourth answer: s is the
+// sequence cut to the byte, so that opos + lit_len + mlen == stop (either
+// part may be empty), and the walk ends there.  What a cut sequence leaves out
+// is not looked at: the literals past the cut need not lie inside the input,
+// and when the literals end exactly at `stop` the match that follows is not
+// read.  A sequence that ends at or before `stop` is judged as next_seq
+// judges it, so a block that ends exactly at `stop` answers kEnd, not kStop,
+// and has passed every test of the full walk.  Output past omax is kBad even
+// where it would also pass `stop`.  With opos >= stop nothing is read.
+enum { kStop = 2 };
+
+template <class Rd>
+LZ4W_HD int next_seq_stop(Rd &rd, uint32_t n, uint32_t &ip, uint32_t opos, uint32_t omax, uint32_t stop, Seq &s)
+{
+    if (n > kMaxBlockIn || opos > omax || stop > omax) return kBad;
+    s.lit_src = ip;
+    s.lit_len = s.off = s.mlen = 0;
+    if (opos >= stop) return kStop;
+    if (ip >= n) return kBad;
+    const uint32_t tok = rd(ip++);
+    uint32_t ll = tok >> 4;
+    if (ll == 15u && !ext_len(rd, n, ip, ll)) return kBad;
+    if (ll > omax - opos) return kBad;
+    s.lit_src = ip;
+    if (ll > stop - opos) {  // the cut falls inside the literals
+        s.lit_len = stop - opos;
+        if (s.lit_len > n - ip) return kBad;
+        return kStop;
+    }
+    if (ll > n - ip) return kBad;
+    s.lit_len = ll;
+    ip += ll;
+    if (ip == n) return (opos != 0 && ll < kLastLiterals) ? kBad : kEnd;
+    const uint32_t pos = opos + ll;
+    if (pos == stop) return kStop;  // a match is at least 4 bytes: none of it is wanted
+    if (n - ip < 2) return kBad;
+    const uint32_t off = rd(ip) | rd(ip + 1) << 8;
+    ip += 2;
+    uint32_t ml = tok & 15u;
+    if (ml == 15u && !ext_len(rd, n, ip, ml)) return kBad;
+    ml += 4;
+    if (off == 0 || off > pos || ml > omax - pos) return kBad;
+    s.off = off;
+    if (ml > stop - pos) {  // the cut falls inside the match
+        s.mlen = stop - pos;
+        return kStop;
+    }
+    s.mlen = ml;
+    return kSeq;
+}
+
 // Byte i of a match of mlen bytes at output position pos with this offset is
 // a copy of the output byte at this index, which lies in [pos - off, pos):
 // an overlapping match (off < mlen) repeats its last off bytes, so no byte of
@@ -111,6 +163,30 @@ LZ4W_HD int64_t decode_block(Rd &rd, uint32_t n, uint8_t *dst, uint32_t omax)
         if (dst)
             for (uint32_t i = 0; i < s.mlen; ++i) dst[opos + i] = dst[match_src(opos, s.off, s.mlen, i)];
         opos += s.mlen;
+    }
+}
+
+// One block in the stop mode, serially: the bytes written (<= stop), or -1.
+// `stopped` says whether the walk ended at the cut (kStop) or at the block's
+// end (kEnd).  Writes dst[0, stop) at most.
+template <class Rd>
+LZ4W_HD int64_t decode_block_stop(Rd &rd, uint32_t n, uint8_t *dst, uint32_t omax, uint32_t stop, bool &stopped)
+{
+    uint32_t ip = 0, opos = 0;
+    stopped = false;
+    for (;;) {
+        Seq s;
+        const int r = next_seq_stop(rd, n, ip, opos, omax, stop, s);
+        if (r < 0) return -1;
+        for (uint32_t i = 0; i < s.lit_len; ++i) dst[opos + i] = uint8_t(rd(s.lit_src + i));
+        opos += s.lit_len;
+        if (r == kEnd) return int64_t(opos);
+        for (uint32_t i = 0; i < s.mlen; ++i) dst[opos + i] = dst[match_src(opos, s.off, s.mlen, i)];
+        opos += s.mlen;
+        if (r == kStop) {
+            stopped = true;
+            return int64_t(opos);
+        }
     }
 }
 

@@ -6,9 +6,12 @@ repository.go:449-466 and 407-429: a state lookup, one ranged packfile read and
 one Decode each).  cdc_restore_files does it per batch of output bytes: every
 distinct blob of the batch is read and decoded once (and, with verify, hashed
 and compared with its checksum), cdc_assemble_device copies it to every place
-it occurs, and writer threads put the files on disk.  Every call goes through
+it occurs, and writer threads put the files on disk.  cdc_restore_ranges reads
+byte ranges of files on the same context (read_ranges, SnapshotFile): a blob
+is decoded only as far as the last byte asked for.  Every call goes through
 the C ABI (cdc_packfile_index, cdc_assemble_device, cdc_restore_*)."""
 import ctypes
+import io
 import os
 
 import numpy as np
@@ -58,6 +61,26 @@ def assemble_device(src, segments, dst, device=None, stream=None):
                                    ln.ctypes.data_as(p64), do.ctypes.data_as(p64), len(so),
                                    ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(s.cuda_stream))
     check(rc, "cdc_assemble_device")
+
+
+def _files(objects, dests=None):
+    """The cdc_restore_file array of the objects, and what must outlive its use."""
+    n = len(objects)
+    files = (_lib.cdc_restore_file * max(n, 1))()
+    keep = []
+    for i, obj in enumerate(objects):
+        chunks = obj.Chunks
+        sums = b"".join(bytes(c.Checksum) for c in chunks)
+        if len(sums) != 32 * len(chunks):
+            raise ValueError("a chunk checksum is 32 bytes (SHA-256)")
+        lens = np.array([int(c.Length) for c in chunks], dtype=np.uint32)
+        sbuf = ctypes.create_string_buffer(sums, max(len(sums), 1))
+        keep.append((sbuf, lens))
+        files[i].path = os.fsencode(dests[i]) if dests is not None else None
+        files[i].nchunks = len(chunks)
+        files[i].checksums = ctypes.cast(sbuf, ctypes.c_void_p)
+        files[i].lengths = lens.ctypes.data if lens.size else None
+    return files, keep
 
 
 class RestoreSession:
@@ -111,20 +134,7 @@ class RestoreSession:
         n = len(objects)
         if dests is not None and len(dests) != n:
             raise ValueError("one destination per object")
-        files = (_lib.cdc_restore_file * max(n, 1))()
-        keep = []
-        for i, obj in enumerate(objects):
-            chunks = obj.Chunks
-            sums = b"".join(bytes(c.Checksum) for c in chunks)
-            if len(sums) != 32 * len(chunks):
-                raise ValueError("a chunk checksum is 32 bytes (SHA-256)")
-            lens = np.array([int(c.Length) for c in chunks], dtype=np.uint32)
-            sbuf = ctypes.create_string_buffer(sums, max(len(sums), 1))
-            keep.append((sbuf, lens))
-            files[i].path = os.fsencode(dests[i]) if dests is not None else None
-            files[i].nchunks = len(chunks)
-            files[i].checksums = ctypes.cast(sbuf, ctypes.c_void_p)
-            files[i].lengths = lens.ctypes.data if lens.size else None
+        files, keep = _files(objects, dests)  # noqa: F841 - keep holds the arrays the call reads
         statuses = [None] * n
         parts = [[] for _ in range(n)]
         errors = []
@@ -147,6 +157,49 @@ class RestoreSession:
             raise errors[0]
         contents = [b"".join(parts[i]) if dests is None and statuses[i] == 0 else None for i in range(n)]
         stats = {name: getattr(st, name) for name, _ in _lib.cdc_restore_stats._fields_}
+        return contents, statuses, stats
+
+    def read_ranges(self, objects, ranges):
+        """cdc_restore_ranges: byte ranges (object index, offset, length) of
+        the objects, each meaning the file's bytes [offset, min(offset +
+        length, size)).  Every blob a batch of ranges touches is decoded once
+        and only as far as the last byte asked for.  Returns (contents,
+        statuses, stats): contents[i] the range's bytes (None for a failed
+        range), statuses[i] 0 or the range's CDC_E_* code (CDC_E_INVALID for
+        an offset past the size), stats the fields of cdc_read_stats."""
+        if not self._h:
+            raise ValueError("session closed")
+        n = len(ranges)
+        rr = (_lib.cdc_read_range * max(n, 1))()
+        for i, r in enumerate(ranges):
+            fi, off, length = (int(v) for v in r)
+            if fi < 0 or off < 0 or length < 0:
+                raise ValueError("a range is (object index, offset, length), none of them negative")
+            rr[i].file, rr[i].offset, rr[i].length = min(fi, 0xFFFFFFFF), off, length
+        files, keep = _files(objects)  # noqa: F841 - keep holds the arrays the call reads
+        statuses = [None] * n
+        parts = [[] for _ in range(n)]
+        errors = []
+
+        def on_range(_ctx, rp):
+            try:
+                r = rp.contents
+                i = int(r.index)
+                statuses[i] = int(r.status)
+                if r.status == 0:
+                    parts[i].append(ctypes.string_at(r.data, int(r.data_len)) if r.data_len else b"")
+            except Exception as e:  # noqa: BLE001 - re-raised after the call
+                errors.append(e)
+
+        cb = _lib.READ_RANGE_FN(on_range)
+        st = _lib.cdc_read_stats()
+        st.struct_size = ctypes.sizeof(st)
+        rc = lib().cdc_restore_ranges(self._h, files, len(objects), rr, n, cb, None, ctypes.byref(st))
+        check(rc, "cdc_restore_ranges")
+        if errors:
+            raise errors[0]
+        contents = [b"".join(parts[i]) if statuses[i] == 0 else None for i in range(n)]
+        stats = {name: getattr(st, name) for name, _ in _lib.cdc_read_stats._fields_ if name not in ("struct_size", "reserved")}
         return contents, statuses, stats
 
     def close(self):
@@ -179,4 +232,104 @@ def restore_files(objects, packfiles, dests=None, key=None, compression="LZ4", v
         return s.run(objects, dests)
 
 
-__all__ = ["packfile_index", "assemble_device", "RestoreSession", "restore_files", "DEFAULT_BATCH_BYTES"]
+def read_ranges(objects, ranges, packfiles, key=None, compression="LZ4", verify=True, writers=8,
+                batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+    """One ranged read through the native pipeline (a RestoreSession for this
+    call only), as restore_files.  Returns what RestoreSession.read_ranges does."""
+    with RestoreSession(key, compression, verify, writers, batch_bytes, device) as s:
+        for p in packfiles:
+            s.add_packfile(p)
+        return s.read_ranges(objects, ranges)
+
+
+class SnapshotFile(io.RawIOBase):
+    """A read-only binary file over one object of a RestoreSession, with
+    VFilep's semantics (snapshot/vfs/vfilep.go:58-122, 168-197): read at the
+    end returns b"", a seek before 0 or past the size raises.  Each device call
+    (session.read_ranges) fetches max(asked, readahead) bytes into a host
+    buffer, and reads are served from that window until they leave it; it is
+    the only cache.  device_calls counts the calls."""
+
+    def __init__(self, session, obj, readahead=4 << 20):
+        super().__init__()
+        if int(readahead) < 0:
+            raise ValueError("readahead is a byte count: not negative")
+        self._s, self._obj, self._ra = session, obj, int(readahead)
+        self._size = sum(int(c.Length) for c in obj.Chunks)
+        self._pos = 0
+        self._win, self._win_off = b"", 0
+        self.device_calls = 0
+
+    @property
+    def size(self):
+        return self._size
+
+    def readable(self):
+        return True
+
+    def seekable(self):
+        return True
+
+    def writable(self):
+        return False
+
+    def tell(self):
+        self._open()
+        return self._pos
+
+    def _open(self):
+        if self.closed:
+            raise ValueError("I/O operation on closed file")
+
+    def seek(self, offset, whence=io.SEEK_SET):
+        self._open()
+        offset = int(offset)
+        if whence == io.SEEK_SET:
+            new = offset
+        elif whence == io.SEEK_CUR:
+            new = self._pos + offset
+        elif whence == io.SEEK_END:
+            new = self._size + offset
+        else:
+            raise ValueError(f"invalid whence ({whence!r})")
+        if new < 0:
+            raise OSError("seek before the start of the file")
+        if new > self._size:
+            raise OSError("seek past the end of the file")
+        self._pos = new
+        return new
+
+    def _fetch(self, n):
+        """n bytes at the position (n <= what is left), through the window."""
+        lo = self._pos - self._win_off
+        if lo < 0 or lo + n > len(self._win):
+            want = min(max(n, self._ra), self._size - self._pos)
+            contents, statuses, _ = self._s.read_ranges([self._obj], [(0, self._pos, want)])
+            self.device_calls += 1
+            if statuses[0] != 0:
+                raise _lib.CdcError(statuses[0], f"read of {want} bytes at {self._pos}")
+            self._win, self._win_off, lo = contents[0], self._pos, 0
+        return self._win[lo:lo + n]
+
+    def read(self, size=-1):
+        self._open()
+        left = self._size - self._pos
+        n = left if size is None or size < 0 else min(int(size), left)
+        if n == 0:
+            return b""
+        data = self._fetch(n)
+        self._pos += len(data)
+        return data
+
+    def readall(self):
+        return self.read(-1)
+
+    def readinto(self, b):
+        m = memoryview(b).cast("B")
+        data = self.read(len(m))
+        m[:len(data)] = data
+        return len(data)
+
+
+__all__ = ["packfile_index", "assemble_device", "RestoreSession", "restore_files", "read_ranges", "SnapshotFile",
+           "DEFAULT_BATCH_BYTES"]
