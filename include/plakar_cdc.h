@@ -957,6 +957,184 @@ int cdc_check_files(cdc_check *c, const cdc_check_file *files, int n, cdc_check_
                     cdc_check_stats *stats);
 void cdc_check_free(cdc_check *c);
 
+/* ---- diff: unified diffs of snapshot files ------------------------------------------
+ * `plakar diff` for two files (cmd/plakar/subcommands/diff/diff.go:152-196):
+ * both files read whole, split with difflib.SplitLines, go-difflib's
+ * UnifiedDiff with Context 3, and "identical" without a read when the two
+ * Object.Checksums are equal.  go-difflib is a port of Python's difflib; the
+ * text here is difflib.unified_diff's (DESIGN.md 5.21 on what is pinned).
+ *
+ * Lines (SplitLines): a text with k newline bytes has k + 1 lines; line j is
+ * the bytes after the j-th newline up to and excluding the next one, or up to
+ * the end of the text; every line is compared and printed as if it ended in
+ * "\n".  An empty text is one empty line.  Every other byte is ordinary. */
+typedef struct cdc_line_rec {
+    uint64_t off;       /* of the line's first byte in the buffer */
+    uint32_t len;       /* without the newline */
+    uint32_t reserved;  /* 0 */
+    uint64_t hash[2];   /* of (len, bytes): equal for equal lines; the values are not part of the interface */
+} cdc_line_rec;
+
+/* The line table of n texts (text_off[i], text_len[i]: host arrays) of one
+ * device buffer: any alignment, texts may overlap, a text is shorter than
+ * 4 GiB.  counts[i] (host, may be NULL) = the lines of text i; d_recs (device,
+ * 16-byte aligned, room for cap records) receives the records of text 0, then
+ * text 1, ...; a line never passes the end of its text.  *total (may be NULL)
+ * = the lines of all texts.  When cap is smaller, CDC_E_NOSPACE with *total
+ * and counts set and nothing written to d_recs.  Three passes: a newline count
+ * per 16-KiB tile, a scan of the tile counts, and the records with their
+ * hashes (a line of cdc_debug_set_line_threshold bytes or more is hashed by a
+ * whole wave).  Synchronous on `stream`.
+ * CDC_E_INVALID before any HIP call: device outside 0..63, NULL arrays with
+ * n > 0, a text outside [0, len) or of 4 GiB or more, d_data NULL with len > 0,
+ * d_recs NULL or misaligned with cap > 0, more than 2^32 - 2 lines possible
+ * (the sum of the text lengths plus n); CDC_E_NOT_INIT before cdc_init; CDC_OK
+ * and nothing launched for n == 0. */
+int cdc_line_table_device(int device, const void *d_data, uint64_t len, const uint64_t *text_off,
+                          const uint64_t *text_len, uint32_t n, cdc_line_rec *d_recs, uint64_t cap, uint64_t *counts,
+                          uint64_t *total, void *stream);
+
+/* Exact line ids.  recs: a host copy of nlines records over d_data; group[g]
+ * .. group[g + 1] (ngroups + 1 ascending entries from 0 to nlines) are the
+ * lines of one pair, A's then B's.  ids[i] = the smallest j in i's group, not
+ * after i, whose line has the same bytes, counted from the group's start.
+ * The first hash_bits bits of the hashes propose (0: all 128); k_line_verify
+ * compares each line's bytes with its candidate's, and flagged lines move on
+ * until none is flagged: *rounds (may be NULL) = the comparison launches.
+ * The hash maps are built on up to 8 host threads, a group per task.
+ * Synchronous on `stream`.  CDC_E_INVALID: NULL arguments, hash_bits outside
+ * 0..128, a group list that does not ascend from 0 to nlines, a record outside
+ * [0, len), nlines of 2^32 - 1 or more. */
+int cdc_line_ids_device(int device, const void *d_data, uint64_t len, const cdc_line_rec *recs, uint64_t nlines,
+                        const uint64_t *group, uint32_t ngroups, int hash_bits, uint32_t *ids, uint32_t *rounds,
+                        void *stream);
+/* Lines of at least this many bytes take the wave-cooperative hash and compare
+ * kernels (0: the default, 4096).  The hashes and ids never depend on it.
+ * Diagnostic.  CDC_OK. */
+int cdc_debug_set_line_threshold(uint32_t bytes);
+
+/* difflib.SequenceMatcher(None, a, b).get_grouped_opcodes(context) over line
+ * ids (autojunk on: with 200 ids or more in b, those that occur more than
+ * len(b) / 100 + 1 times do not start matches).  ops[0, cap) receives the
+ * opcodes of all groups, `group` counting the groups from 0; *nops their
+ * number.  CDC_E_NOSPACE with *nops set when cap is smaller.  Host only; needs
+ * no cdc_init.  CDC_E_INVALID: NULL arrays with a nonzero count, context < 0,
+ * 2^32 - 1 ids or more.  The worst case is quadratic, as the reference's. */
+#define CDC_DIFF_EQUAL 0
+#define CDC_DIFF_REPLACE 1
+#define CDC_DIFF_DELETE 2
+#define CDC_DIFF_INSERT 3
+typedef struct cdc_diff_op {
+    uint32_t tag, group;
+    uint32_t i1, i2, j1, j2;  /* a[i1:i2] and b[j1:j2] */
+} cdc_diff_op;
+int cdc_diff_script(const uint32_t *a_ids, uint64_t na, const uint32_t *b_ids, uint64_t nb, int context,
+                    cdc_diff_op *ops, uint64_t cap, uint64_t *nops);
+
+/* An emit record: at dst_off the prefix byte (CDC_EMIT_PREFIX: flags & 0xff),
+ * then len bytes from src_off of the plaintext or (CDC_EMIT_LITERAL) the
+ * literal area, then "\n" (CDC_EMIT_NEWLINE). */
+#define CDC_EMIT_PREFIX 0x100u
+#define CDC_EMIT_LITERAL 0x200u
+#define CDC_EMIT_NEWLINE 0x400u
+typedef struct cdc_emit_rec {
+    uint64_t src_off, dst_off;
+    uint32_t len, flags;
+} cdc_emit_rec;
+/* The unified diff of one pair as an emit plan: "--- from\n+++ to\n" before
+ * the first hunk, per group "@@ -r1 +r2 @@\n" (difflib's range format) and the
+ * lines with ' ', '-', '+', all '-' of a replace before its '+'; no group, no
+ * output.  The header and @@ lines are literals, written to lit[0, lit_cap)
+ * and addressed from lit_base; destinations ascend from dst_base.  *nrecs,
+ * *lit_bytes, *out_bytes (each may be NULL) are always set; CDC_E_NOSPACE when
+ * rec_cap or lit_cap is smaller (then nothing is written).  Host only. */
+int cdc_diff_emit_plan(const cdc_diff_op *ops, uint64_t nops, const cdc_line_rec *a_lines, uint64_t na,
+                       const cdc_line_rec *b_lines, uint64_t nb, const char *from_name, const char *to_name,
+                       uint64_t dst_base, uint64_t lit_base, cdc_emit_rec *recs, uint64_t rec_cap, uint8_t *lit,
+                       uint64_t lit_cap, uint64_t *nrecs, uint64_t *lit_bytes, uint64_t *out_bytes);
+/* Execute an emit plan: n records (host array; copied before the call
+ * returns) over the plaintext [d_plain, + plain_cap) and the literal area
+ * [d_lit, + lit_cap), into [d_dst, + dst_cap).  Records are short and many:
+ * a wave takes up to 64 of them with its lanes over their output bytes; a
+ * record of 2 KiB or more goes in 16-KiB pieces of 16-byte stores.  Exactly
+ * the bytes of the records are written.  Asynchronous on `stream`.
+ * CDC_E_INVALID before any HIP call: NULL arguments, a source range outside
+ * its area, a destination outside [0, dst_cap), destinations that do not
+ * ascend or that overlap, unknown flag bits, more than 2^32 - 1 records, or a
+ * destination that overlaps a source area.  CDC_OK and nothing launched for
+ * n == 0. */
+int cdc_diff_emit_device(int device, const void *d_plain, uint64_t plain_cap, const void *d_lit, uint64_t lit_cap,
+                         const cdc_emit_rec *recs, uint64_t n, void *d_dst, uint64_t dst_cap, void *stream);
+
+/* A diff context, shaped like a check context. */
+typedef struct cdc_diff_opts {
+    uint32_t struct_size;   /* sizeof(cdc_diff_opts) */
+    int compress;           /* CDC_COMPRESS_NONE, _LZ4 or _GZIP */
+    const uint8_t *key;     /* 32-byte repository key, or NULL */
+    int context;            /* lines of context (0: 3) */
+    int threads;            /* reader and matcher threads (0: 8) */
+    uint64_t batch_bytes;   /* of file bytes per batch (0: 256 MiB; at most 1 GiB) */
+    uint64_t max_lines;     /* per batch (0: 16 Mi) */
+    int hash_bits;          /* diagnostic: only so many bits of the line hashes propose (0: all 128) */
+} cdc_diff_opts;
+/* struct_size set, everything else 0. */
+void cdc_diff_default_opts(cdc_diff_opts *out);
+typedef struct cdc_diff_pair {
+    cdc_check_file a, b;    /* the two versions; object_checksum may be NULL */
+    const char *from_name, *to_name;
+} cdc_diff_pair;
+typedef struct cdc_diff_result {
+    int index;              /* position in pairs */
+    int status;             /* CDC_OK, CDC_E_NOTFOUND, CDC_E_NOSPACE, CDC_E_IO, CDC_E_MISMATCH or a blob's Decode error */
+    int bad_side;           /* 0: a, 1: b, -1: none */
+    int identical;          /* no hunk: equal checksums or chunk lists, or equal lines */
+    int64_t bad_chunk;      /* the chunk `status` names on bad_side, or -1 */
+    uint64_t a_lines, b_lines;  /* 0 for a pair that was not read */
+    uint64_t hunks;
+    const uint8_t *text;    /* the unified diff, valid during the call */
+    uint64_t text_len;
+} cdc_diff_result;
+typedef struct cdc_diff_stats {
+    uint32_t struct_size;   /* set by the caller; at most that many bytes are written */
+    uint32_t reserved;
+    uint64_t pairs, failed_pairs, identical_pairs, skipped_pairs;  /* skipped: identical without device work */
+    uint64_t bytes, segments;  /* file bytes and chunk occurrences of the batches */
+    uint64_t distinct_blobs, decoded_blobs, encoded_bytes, decoded_bytes, batches;  /* as cdc_check_stats */
+    uint64_t lines, distinct_lines, verify_rounds, hunks, out_bytes;
+    double read_s, h2d_s, decode_s, verify_s, assemble_s, table_s, ids_s, match_s, emit_s, d2h_s;
+    double wall_s;
+} cdc_diff_stats;
+typedef void (*cdc_diff_pair_fn)(void *ctx, const cdc_diff_result *r);
+typedef struct cdc_diff cdc_diff;
+/* CDC_E_INVALID: NULL, a struct_size that is not this header's, a device
+ * outside 0..63, an unknown compress, context < 0, threads outside 0..256,
+ * batch_bytes over 1 GiB, max_lines over 2^31, hash_bits outside 0..128;
+ * CDC_E_NOT_INIT before cdc_init. */
+int cdc_diff_new(int device, const cdc_diff_opts *opts, cdc_diff **out);
+int cdc_diff_add_packfile(cdc_diff *d, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
+int cdc_diff_add_packfile_path(cdc_diff *d, const char *path);
+/* The unified diffs of n pairs.  A pair whose two object checksums are given
+ * and equal, or whose chunk lists are equal, is identical with no device work
+ * (diff.go:156).  The others go in batches of whole pairs of at most
+ * batch_bytes of file bytes: reader threads gather the distinct encoded blobs
+ * of both sides, one upload, one Decode with SHA-256 and compare over the
+ * distinct blobs (restore's plan, Check's calls), both images laid out by
+ * cdc_assemble_device, the line table, exact ids, the matcher on `threads`
+ * host threads (one pair per task), the emit plan, cdc_diff_emit_device and
+ * one copy back of the batch's diff text.  The stages of a batch run in
+ * sequence.  on_pair (may be NULL) is called once per pair from the calling
+ * thread.  Failures are per pair and the run goes on: CDC_E_NOTFOUND with
+ * bad_side and bad_chunk for a chunk in no packfile; a blob that cannot be
+ * read, fails Decode or has the wrong Length or SHA-256 fails every pair that
+ * uses it (bad_side, bad_chunk: the first such chunk, a's before b's), and no
+ * other; a pair whose two sizes exceed batch_bytes or whose lines exceed
+ * max_lines fails alone with CDC_E_NOSPACE.  Returns CDC_OK, or the run's own
+ * first failure; CDC_E_INVALID (NULL context or pairs, a file with chunks and
+ * no arrays, stats->struct_size < 8) before the device is touched. */
+int cdc_diff_files(cdc_diff *d, const cdc_diff_pair *pairs, int n, cdc_diff_pair_fn on_pair, void *ctx,
+                   cdc_diff_stats *stats);
+void cdc_diff_free(cdc_diff *d);
+
 /* ---- archive: a snapshot's entries as one tar or tar.gz stream -------------------
  * `plakar archive` (cmd/plakar/subcommands/archive/archive.go) for its tar and
  * tarball formats.  The caller supplies the entries (it walks the snapshot, as

@@ -13,6 +13,8 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
     plakar_amd.restore     packfiles and object records back to files (RestoreSession, restore_files)
     plakar_amd.check       chunks and object checksums verified on the device (CheckSession, check_files,
                            object_digests_device)
+    plakar_amd.diff        unified diffs of pairs of files (DiffSession, diff_files; line_table_device,
+                           line_ids_device, diff_script, diff_emit_device)
     plakar_amd.sync        blobs of one repository as blobs of another, on the device: re-key and
                            re-encode (transcode_device), synchronize()'s loop over packfiles (SyncSession)
     plakar_amd.archive     a snapshot's entries as one tar or tar.gz stream (ArchiveSession, archive_files);
@@ -20,4 +22,4 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "sync", "archive", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "archive", "build"]

@@ -203,6 +203,53 @@ class cdc_check_stats(ctypes.Structure):
                                                "wall_s")]
 
 
+class cdc_line_rec(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("hash", ctypes.c_uint64 * 2)]
+
+
+class cdc_diff_op(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("tag", "group", "i1", "i2", "j1", "j2")]
+
+
+class cdc_emit_rec(ctypes.Structure):
+    _fields_ = [("src_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("len", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
+class cdc_diff_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
+                ("context", ctypes.c_int), ("threads", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
+                ("max_lines", ctypes.c_uint64), ("hash_bits", ctypes.c_int)]
+
+
+class cdc_diff_pair(ctypes.Structure):
+    _fields_ = [("a", cdc_check_file), ("b", cdc_check_file), ("from_name", ctypes.c_char_p),
+                ("to_name", ctypes.c_char_p)]
+
+
+class cdc_diff_result(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_int), ("status", ctypes.c_int), ("bad_side", ctypes.c_int),
+                ("identical", ctypes.c_int), ("bad_chunk", ctypes.c_int64), ("a_lines", ctypes.c_uint64),
+                ("b_lines", ctypes.c_uint64), ("hunks", ctypes.c_uint64), ("text", ctypes.POINTER(ctypes.c_uint8)),
+                ("text_len", ctypes.c_uint64)]
+
+
+class cdc_diff_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("pairs", "failed_pairs", "identical_pairs", "skipped_pairs", "bytes",
+                                               "segments", "distinct_blobs", "decoded_blobs", "encoded_bytes",
+                                               "decoded_bytes", "batches", "lines", "distinct_lines", "verify_rounds",
+                                               "hunks", "out_bytes")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "assemble_s", "table_s",
+                                               "ids_s", "match_s", "emit_s", "d2h_s", "wall_s")]
+
+
+# CDC_DIFF_* and CDC_EMIT_* of the header, without the prefix: a module name that starts with CDC_ is a status code
+DIFF_EQUAL, DIFF_REPLACE, DIFF_DELETE, DIFF_INSERT = 0, 1, 2, 3
+EMIT_PREFIX, EMIT_LITERAL, EMIT_NEWLINE = 0x100, 0x200, 0x400
+
+
 class cdc_archive_opts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
                 ("verify", ctypes.c_int), ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64),
@@ -242,6 +289,7 @@ ARCHIVE_ENTRY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.
 RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_restore_result))
 READ_RANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_read_result))
 CHECK_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_check_result))
+DIFF_PAIR_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_diff_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 
@@ -403,6 +451,30 @@ SIGNATURES = {
     "cdc_check_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_check_file), ctypes.c_int, CHECK_FILE_FN,
                                        ctypes.c_void_p, _P(cdc_check_stats)]),
     "cdc_check_free": (None, [ctypes.c_void_p]),
+    "cdc_line_table_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                             _P(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                             _P(ctypes.c_uint64), _P(ctypes.c_uint64), ctypes.c_void_p]),
+    "cdc_line_ids_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_uint64, _P(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_int,
+                                           _P(ctypes.c_uint32), _P(ctypes.c_uint32), ctypes.c_void_p]),
+    "cdc_debug_set_line_threshold": (ctypes.c_int, [ctypes.c_uint32]),
+    "cdc_diff_script": (ctypes.c_int, [_P(ctypes.c_uint32), ctypes.c_uint64, _P(ctypes.c_uint32), ctypes.c_uint64,
+                                       ctypes.c_int, _P(cdc_diff_op), ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_diff_emit_plan": (ctypes.c_int, [_P(cdc_diff_op), ctypes.c_uint64, _P(cdc_line_rec), ctypes.c_uint64,
+                                          _P(cdc_line_rec), ctypes.c_uint64, ctypes.c_char_p, ctypes.c_char_p,
+                                          ctypes.c_uint64, ctypes.c_uint64, _P(cdc_emit_rec), ctypes.c_uint64,
+                                          ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_uint64),
+                                          _P(ctypes.c_uint64)]),
+    "cdc_diff_emit_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_uint64, _P(cdc_emit_rec), ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_uint64, ctypes.c_void_p]),
+    "cdc_diff_default_opts": (None, [_P(cdc_diff_opts)]),
+    "cdc_diff_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_diff_opts), _P(ctypes.c_void_p)]),
+    "cdc_diff_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_diff_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_diff_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_diff_pair), ctypes.c_int, DIFF_PAIR_FN,
+                                      ctypes.c_void_p, _P(cdc_diff_stats)]),
+    "cdc_diff_free": (None, [ctypes.c_void_p]),
     "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
     "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_new_zip": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),

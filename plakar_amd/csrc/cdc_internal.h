@@ -189,6 +189,10 @@ int launch_object_digests(const ObjBatch &B, void *stream);
 int object_digests(int device, const void *d_data, uint64_t len, const uint64_t *seg_off, const uint64_t *seg_len,
                    uint64_t nsegs, const uint64_t *obj_seg0, uint32_t n, uint8_t *d_digests, void *stream,
                    uint64_t *seam_bytes);
+// cdc_diff.hip: cdc_line_ids_device after its argument checks, with the hash maps built on `threads` host
+// threads, a group per task (the public call takes 8).
+int line_ids(int device, const void *d_data, const cdc_line_rec *recs, uint64_t nlines, const uint64_t *group,
+             uint32_t ngroups, int hash_bits, uint32_t *ids, uint32_t *rounds, void *stream, int threads);
 double host_sha256_rate();  // cdc_api.cpp: one host core's SHA-256 bytes per second, measured once
 extern uint64_t g_digest_lanes;
 // The calling thread's scan mode for make_plan: -1 the default (static grid,
