@@ -53,6 +53,7 @@ constexpr uint32_t kEmitLong = 2048;        // a record this long goes in pieces
 constexpr uint32_t kEmitPiece = 16384;
 constexpr uint32_t kEmitUnitBytes = 8192;   // output bytes of a unit of short records
 constexpr int kBlocksPerCU = 8;
+constexpr int kEmitBlocksPerCU = 32;        // k_diff_emit: one wave per workgroup
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_u __attribute__((aligned(1)));
@@ -626,7 +627,7 @@ static int emit(int device, const uint8_t *d_plain, const uint8_t *d_lit, const 
     std::memcpy(h + o_recs, recs, sizeof(cdc_emit_rec) * size_t(n));
     std::memcpy(h + o_units, units.data(), sizeof(Unit) * units.size());
     if (hipMemcpyAsync(d, h, c.bytes(), hipMemcpyHostToDevice, st) != hipSuccess) return CDC_E_DEVICE;
-    const uint32_t grid = uint32_t(std::min<uint64_t>(units.size(), uint64_t(cdc::device_cus(device)) * 32));
+    const uint32_t grid = uint32_t(std::min<uint64_t>(units.size(), uint64_t(cdc::device_cus(device)) * kEmitBlocksPerCU));
     hipLaunchKernelGGL(k_diff_emit, dim3(grid), dim3(64), 0, st, d_plain, d_lit, reinterpret_cast<const cdc_emit_rec *>(d + o_recs),
                        reinterpret_cast<const Unit *>(d + o_units), uint32_t(units.size()), d_dst);
     S.used = true;  // even when the launch failed: the copy above reads the slot

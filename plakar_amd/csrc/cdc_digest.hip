@@ -706,6 +706,7 @@ __global__ __launch_bounds__(kDigestWaves * 64) void k_object_digest(const ObjBa
 // copy only collide on equal bytes); then the copies are summed, one uint4
 // of bins per lane, into the chunk's row.
 constexpr uint32_t kHistWaves = 4, kHistCopies = 8;
+constexpr uint32_t kHistBlocksPerCU = 8;  // the grid's cap: past it a wave takes a further chunk
 
 template <bool kInd>
 __global__ __launch_bounds__(kHistWaves * 64) void k_chunk_hist(const DigestBatch DB)
@@ -814,6 +815,7 @@ __device__ __forceinline__ double go_log2_dev(double x)
 // KiB per row), computes their terms, and the wave folds them in bin order
 // (the reference's sequential e -= term: a fixed order, so bit-exact).
 constexpr uint32_t kEntWaves = 4;
+constexpr uint32_t kEntMaxBlocks = 2048;  // the grid's cap: past it a wave takes a further row
 __global__ __launch_bounds__(kEntWaves * 64) void k_chunk_entropy(const uint32_t *__restrict__ hist, uint64_t rows,
                                                                   double *__restrict__ out)
 {
@@ -849,7 +851,7 @@ __global__ __launch_bounds__(kEntWaves * 64) void k_chunk_entropy(const uint32_t
 int launch_entropy(const uint32_t *d_hist, uint64_t rows, double *d_out, void *stream)
 {
     if (!rows) return CDC_OK;
-    const uint64_t wgs = std::min<uint64_t>((rows + kEntWaves - 1) / kEntWaves, 256u * 8u);
+    const uint64_t wgs = std::min<uint64_t>((rows + kEntWaves - 1) / kEntWaves, kEntMaxBlocks);
     hipLaunchKernelGGL(k_chunk_entropy, dim3(uint32_t(wgs)), dim3(kEntWaves * 64), 0,
                        reinterpret_cast<hipStream_t>(stream), d_hist, rows, d_out);
     return hipGetLastError() == hipSuccess ? CDC_OK : CDC_E_DEVICE;
@@ -907,7 +909,7 @@ int launch_digest_kernels(DigestBatch D, uint64_t cap, bool hist, hipStream_t st
         hipLaunchKernelGGL(k_chunk_digest<kInd>, dim3(uint32_t((cap + lanes_per_wg - 1) / lanes_per_wg), D.nbufs),
                            dim3(kDigestWaves * 64), 0, st, D);
     if (hist && (parts & 2)) {  // a wave per chunk; up to 8 workgroups per CU
-        const uint64_t wgs = std::min<uint64_t>((cap + kHistWaves - 1) / kHistWaves, uint64_t(cus) * 8u);
+        const uint64_t wgs = std::min<uint64_t>((cap + kHistWaves - 1) / kHistWaves, uint64_t(cus) * kHistBlocksPerCU);
         hipLaunchKernelGGL(k_chunk_hist<kInd>, dim3(uint32_t(wgs), D.nbufs), dim3(kHistWaves * 64), 0, st, D);
     }
     return hipGetLastError() == hipSuccess ? CDC_OK : CDC_E_DEVICE;

@@ -149,6 +149,45 @@ def test_line_content_edge_cases():
     assert r.size == len(lines)
 
 
+def _variant_positions(n, rng):
+    """Every position of a line of up to 600 bytes; of a longer one the first
+    600, the first and last byte of each 8-byte word next to a 256-byte block
+    edge, the last byte, and 200 seeded positions."""
+    if n <= 600:
+        return list(range(n))
+    at = set(range(600))
+    for edge in range(256, n + 1, 256):
+        at.update(p for p in (edge - 8, edge - 1, edge, edge + 7) if p < n)
+    at.add(n - 1)
+    at.update(int(p) for p in rng.integers(600, n, 200))
+    return sorted(at)
+
+
+def test_every_byte_and_the_length_reach_the_hash():
+    """A line and its single-byte variants, at every position a word, a block
+    or a wave step can drop, and lines of 1-17 zero bytes (equal but for their
+    length): all hashes differ, on both paths, so a hash that left a position
+    out would show here and not only as slow diffs.  With 4 hash bits the byte
+    comparison meets a difference at each of those positions."""
+    rng = np.random.default_rng(41)
+    lengths = list(range(1, 25)) + [255, 256, 257, 511, 512, 513, 4095, 4096, 4097, 16383, 16384, 16385]
+    lines = []
+    for n in lengths:
+        x = rng.integers(11, 256, n, dtype=np.uint8)  # neither a newline nor a zero
+        lines.append(x.tobytes())
+        for p in _variant_positions(n, rng):
+            y = x.copy()
+            y[p] = x[p] + 1 if x[p] < 255 else 11
+            lines.append(y.tobytes())
+    lines += [b"\0" * k for k in range(1, 18)]
+    assert len(set(lines)) == len(lines) > 5000
+    buf = b"\n".join(lines)
+    r = _run(buf, [(0, len(buf))], thresholds=(0, LANE, WAVE))
+    assert r["len"].tolist() == [len(ln) for ln in lines]
+    hashes = set(map(tuple, r["hash"].tolist()))
+    assert len(hashes) == len(lines), f"{len(lines) - len(hashes)} lines share a 128-bit hash with another"
+
+
 def test_seventy_thousand_short_lines():
     """More tiles than one pass of the scan's workgroup takes (256), so the
     running sum is carried; lengths 0-130 from an alphabet of 3."""
