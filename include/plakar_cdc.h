@@ -1135,6 +1135,104 @@ int cdc_diff_files(cdc_diff *d, const cdc_diff_pair *pairs, int n, cdc_diff_pair
                    cdc_diff_stats *stats);
 void cdc_diff_free(cdc_diff *d);
 
+/* ---- sync: packfiles of one repository in, packfiles of another out ----------------
+ * The loop of synchronize (cmd/plakar/subcommands/sync/sync.go:182-266): for
+ * every blob the destination lacks, GetBlob from the source, PutBlob
+ * (snapshot/blobs.go:9-24) into the destination, whose packerJob
+ * (snapshot/snapshot.go:51-92) writes packfiles.  Here it is a pipeline over
+ * batches of stored blobs whose device work is cdc_transcode_device_level.
+ *
+ * Which rows a run takes: every index row of the registered packfiles, in
+ * registration and index order, of every blob type.  A row is skipped when its
+ * (type, checksum) is in `known` or was already taken in this run, and, when
+ * `wanted` is given, unless it is in `wanted`.  One checksum under two types is
+ * two blobs.  known and wanted are 33-byte records, the type byte then the
+ * checksum, sorted ascending by memcmp (equal neighbours are accepted).
+ * A batch is rows up to batch_bytes of stored bytes; a larger blob goes alone;
+ * a stored length of 0 is a legal row and is carried (an empty chunk of a
+ * repository with no key and no compression is stored that way). */
+#define CDC_SYNC_PATH_COPY 0      /* the path cdc_transcode_device takes between the two codecs */
+#define CDC_SYNC_PATH_REKEY 1
+#define CDC_SYNC_PATH_OPEN 2
+#define CDC_SYNC_PATH_SEAL 3
+#define CDC_SYNC_PATH_REENCODE 4
+typedef struct cdc_sync_opts {
+    uint32_t struct_size;      /* sizeof(cdc_sync_opts) */
+    cdc_codec src, dst;        /* the two repositories; the keys are copied */
+    int verify;                /* not 0: the index checksums are checked first (cdc_transcode_device's `checksums`) */
+    int level;                 /* CDC_LEVEL_*; the re-encode path only */
+    uint32_t packfile_max;     /* 0: 20 MiB */
+    uint64_t batch_bytes;      /* stored bytes per batch (0: 64 MiB) */
+    int readers, packers;      /* threads (0: 8 each) */
+    int64_t timestamp;         /* packfile footer timestamp */
+    const uint8_t *known;      /* the destination's BlobExists: sorted 33-byte records, copied; or NULL */
+    uint64_t nknown;
+} cdc_sync_opts;
+/* struct_size set, verify = 1, everything else 0 (both codecs CDC_COMPRESS_NONE without a key). */
+void cdc_sync_default_opts(cdc_sync_opts *out);
+typedef struct cdc_sync_stats {
+    uint32_t struct_size;      /* set by the caller; at most that many bytes are written */
+    int32_t path;              /* CDC_SYNC_PATH_* */
+    uint64_t blobs, skipped, failed;  /* rows taken; rows known or already taken; taken rows that failed */
+    uint64_t bytes_in, bytes_out;     /* stored bytes of the rows taken; of the blobs written */
+    uint64_t batches, packfiles, packed_bytes;
+    /* wall time of each stage, summed over the batches: read (the gather),
+     * h2d, transcode (the check included), d2h, pack (the packers' step and the
+     * last flush, callbacks excluded), callback (inside on_pack and on_fail) */
+    double read_s, h2d_s, transcode_s, d2h_s, pack_s, callback_s;
+    double device_wait_s;      /* the calling thread waiting for a batch's reads and upload (device idle) */
+    double wall_s;
+} cdc_sync_stats;
+/* A blob of the run that failed: CDC_E_IO (it could not be read), or its
+ * status from cdc_transcode_device (CDC_E_AUTH, CDC_E_CORRUPT, CDC_E_UNSUPPORTED,
+ * CDC_E_MISMATCH). */
+typedef void (*cdc_sync_blob_fn)(void *ctx, uint8_t type, const uint8_t checksum[32], int status);
+/* A sync context: the two codecs, `known`, the registered packfiles, three
+ * streams, two input and two output slots and its packers, kept across runs.
+ * CDC_E_INVALID before the device is touched: NULL, a struct_size that is not
+ * this header's, a device outside 0..63, an unknown compress or level, readers
+ * or packers outside 0..256, known NULL with nknown > 0 or unsorted;
+ * CDC_E_NOT_INIT before cdc_init. */
+typedef struct cdc_sync cdc_sync;
+int cdc_sync_new(int device, const cdc_sync_opts *opts, cdc_sync **out);
+int cdc_sync_add_packfile(cdc_sync *s, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
+int cdc_sync_add_packfile_path(cdc_sync *s, const char *path);
+/* One sync of the registered packfiles.  Three stages, batch k + 1 read and
+ * uploaded while batch k is on the device and batch k - 1 is downloaded and
+ * packed:
+ *   reader   gathers the batch's stored blobs into a pinned arena (memcpy, or
+ *            pread for a packfile registered by path, on `readers` threads)
+ *            and uploads it; a blob that cannot be read fails alone, CDC_E_IO;
+ *   device   (the calling thread) one cdc_transcode_device_level call over the
+ *            batch's blobs, with their index checksums when verify is set and
+ *            fresh OS random bytes (getrandom) when dst has a key; the output
+ *            buffer grows and the call is repeated on CDC_E_NOSPACE;
+ *   packers  one download into pinned memory, then `packers` threads append the
+ *            surviving blobs with their type and checksum (cdc_packer_add_blob),
+ *            each to its own packfile; a batch's blobs are split among them in
+ *            contiguous ranges, so every packfile holds its rows in source
+ *            order.  A packer hands its packfile to on_pack (PutPackfile) when
+ *            cdc_packer_add_blob returns 1, and the rest at the end of the run,
+ *            packer by packer.  With packers = 1 the packfiles are those of the
+ *            loop above run blob by blob; without dst.key their bytes depend
+ *            on nothing else.
+ * on_pack calls are serialised; the bytes are valid during the call.  A
+ * negative status from on_pack stops the run: that status is returned and
+ * on_pack is not called again.  on_fail (may be NULL) is called once per failed
+ * blob, from one library thread; a failed blob contributes no bytes and the
+ * run goes on.  The reference aborts the snapshot at the first failed GetBlob:
+ * a caller must not commit the destination snapshot after a failure.
+ * wanted: nwanted sorted 33-byte records, or NULL: every row.  stats may be
+ * NULL.  One run at a time per context; a context can run again, and each
+ * run's taken-set starts empty.  Returns CDC_OK, or the run's own first
+ * failure (a device error, on_pack's status); CDC_E_INVALID before the device
+ * is touched: NULL s or on_pack, wanted unsorted, stats->struct_size < 8.
+ * Out of scope: the PutPackfile stored form on either side, the snapshot,
+ * state and header records, more than one device. */
+int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack,
+                 cdc_sync_blob_fn on_fail, void *ctx, cdc_sync_stats *stats);
+void cdc_sync_free(cdc_sync *s);
+
 /* ---- archive: a snapshot's entries as one tar or tar.gz stream -------------------
  * `plakar archive` (cmd/plakar/subcommands/archive/archive.go) for its tar and
  * tarball formats.  The caller supplies the entries (it walks the snapshot, as

@@ -133,6 +133,21 @@ class cdc_codec(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_char_p)]
 
 
+class cdc_sync_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("src", cdc_codec), ("dst", cdc_codec), ("verify", ctypes.c_int),
+                ("level", ctypes.c_int), ("packfile_max", ctypes.c_uint32), ("batch_bytes", ctypes.c_uint64),
+                ("readers", ctypes.c_int), ("packers", ctypes.c_int), ("timestamp", ctypes.c_int64),
+                ("known", ctypes.c_void_p), ("nknown", ctypes.c_uint64)]
+
+
+class cdc_sync_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("path", ctypes.c_int32)] + \
+               [(n, ctypes.c_uint64) for n in ("blobs", "skipped", "failed", "bytes_in", "bytes_out", "batches",
+                                               "packfiles", "packed_bytes")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "transcode_s", "d2h_s", "pack_s", "callback_s",
+                                               "device_wait_s", "wall_s")]
+
+
 class cdc_restore_opts(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_void_p), ("verify", ctypes.c_int),
                 ("writers", ctypes.c_int), ("batch_bytes", ctypes.c_uint64)]
@@ -292,6 +307,7 @@ CHECK_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_check
 DIFF_PAIR_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_diff_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
+SYNC_BLOB_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint8, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int)
 
 CUT_DTYPE_FIELDS = [("offset", "<u8"), ("length", "<u4"), ("reserved", "<u4")]
 READ_FN = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
@@ -475,6 +491,13 @@ SIGNATURES = {
     "cdc_diff_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_diff_pair), ctypes.c_int, DIFF_PAIR_FN,
                                       ctypes.c_void_p, _P(cdc_diff_stats)]),
     "cdc_diff_free": (None, [ctypes.c_void_p]),
+    "cdc_sync_default_opts": (None, [_P(cdc_sync_opts)]),
+    "cdc_sync_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_sync_opts), _P(ctypes.c_void_p)]),
+    "cdc_sync_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_sync_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_sync_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, BACKUP_PACK_FN, SYNC_BLOB_FN,
+                                    ctypes.c_void_p, _P(cdc_sync_stats)]),
+    "cdc_sync_free": (None, [ctypes.c_void_p]),
     "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
     "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_new_zip": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),

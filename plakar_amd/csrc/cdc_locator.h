@@ -2,7 +2,8 @@
 // registered packfiles, in memory or by path, and checksum -> (packfile,
 // offset, length) for every TYPE_CHUNK row (state.GetSubpartForBlob,
 // repository/repository.go:449-466); a checksum already there keeps its first
-// location.  Host only.
+// location.  Sync registers packfiles the same way and keeps their whole
+// indexes instead (keep_rows).  Host only.
 #pragma once
 
 #include <fcntl.h>
@@ -71,11 +72,22 @@ struct Locator {
     std::unordered_map<Sum, uint32_t, SumHash> index;  // checksum -> blob id
     std::vector<Loc> locs;                             // by blob id
     std::vector<Sum> sums;                             // by blob id
+    // Sync walks every row of every type in index order and looks nothing up
+    // by checksum: with keep_rows each packfile's whole index is kept in
+    // rows[pack] and the checksum index above stays empty.
+    bool keep_rows = false;
+    std::vector<std::vector<cdc_packfile_row>> rows;
 
     static void sha(const void *data, size_t n, uint8_t out[32]) { cdc::sha256(data, n, out); }
 
     void add_rows(Pack &&P, const std::vector<cdc_packfile_row> &rows)
     {
+        if (keep_rows) {  // both lists grow or neither does
+            packs.reserve(packs.size() + 1);
+            this->rows.push_back(rows);
+            packs.push_back(std::move(P));
+            return;
+        }
         const uint32_t pack = uint32_t(packs.size());
         packs.push_back(std::move(P));
         for (const cdc_packfile_row &r : rows) {

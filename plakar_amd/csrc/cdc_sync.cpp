@@ -1,0 +1,530 @@
+// cdc_sync_*: packfiles of one repository in, packfiles of another out
+// (include/plakar_cdc.h, "sync").
+//
+// The reference's synchronize (cmd/plakar/subcommands/sync/sync.go:182-266)
+// moves one blob at a time: GetBlob decodes it with the source's compression
+// and key, PutBlob (snapshot/blobs.go:9-24) encodes it with the destination's
+// and hands it to the packer channel, and packerJob (snapshot/snapshot.go:
+// 51-92) appends it to a packfile that is flushed once Size() > MaxSize.  Here
+// a run is a pipeline over batches of stored blobs planned up front
+// (sync_plan.h), three stages on three threads and three streams:
+//
+//   reader   gathers the batch's stored blobs into a pinned arena (memcpy or
+//            pread, on `readers` threads) and uploads it;
+//   device   (the calling thread) one cdc_transcode_device_level call over the
+//            blobs that were read: the check when verify is set, then the
+//            re-key, open, seal, copy or re-encode;
+//   packers  downloads the batch's output into a pinned slot, reports the
+//            failed blobs, and `packers` threads append the surviving ones to
+//            their own packfiles (cdc_packer_*), each handed to on_pack when
+//            AddBlob says so and at the end.
+//
+// Two input slots and two output slots rotate: batch k + 1 is read and
+// uploaded while batch k is on the device and batch k - 1 is downloaded and
+// packed.  Transcode is synchronous and holds the per-device workspace, so the
+// device stages of two batches never overlap.
+#include <fcntl.h>
+#include <hip/hip_runtime.h>
+#include <sys/random.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "cdc_hostmem.h"
+#include "cdc_internal.h"
+#include "cdc_locator.h"
+#include "sync_plan.h"
+#include "transcode_plan.h"
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+template <class F>
+static void parallel_for(int threads, size_t n, F fn)
+{
+    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
+    if (t <= 1) {
+        for (size_t i = 0; i < n; ++i) fn(i);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+}
+
+static int random_bytes(uint8_t *p, size_t n)
+{
+    while (n) {
+        const ssize_t k = getrandom(p, n, 0);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) return CDC_E_IO;
+        p += k;
+        n -= size_t(k);
+    }
+    return CDC_OK;
+}
+
+static bool compress_ok(int c) { return c == CDC_COMPRESS_NONE || c == CDC_COMPRESS_LZ4 || c == CDC_COMPRESS_GZIP; }
+
+struct InSlot {   // reader -> device stage
+    cdc::PinBuf h;
+    cdc::DevBuf d;
+    std::vector<uint64_t> eoff, elen;  // the batch's stored blobs in the arena
+    std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
+};
+struct OutSlot {  // device stage -> packers
+    cdc::DevBuf d;
+    cdc::PinBuf h;
+    std::vector<uint64_t> off;   // n + 1: the batch's blobs in the output; a failed one has no bytes
+    std::vector<int32_t> status; // n
+};
+
+}  // namespace
+
+struct cdc_sync {
+    int device = 0;
+    cdc_sync_opts o{};
+    std::vector<uint8_t> skey, dkey, known;
+    cdc_codec src{}, dst{};
+    cdc::Locator loc;  // the registered packfiles and their whole indexes (keep_rows)
+    hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stage, download
+    InSlot in[2];
+    OutSlot out[2];
+    std::vector<cdc_packer *> packers;
+    std::mutex run_mu;
+};
+
+namespace {
+
+struct Run {
+    cdc_sync *S;
+    cdc_backup_pack_fn on_pack;
+    cdc_sync_blob_fn on_fail;
+    void *ctx;
+    splan::Plan plan;
+    // the stages' hand-offs: counts of batches past each point
+    std::mutex mu;
+    std::condition_variable cv;
+    int uploaded = 0, consumed = 0, transcoded = 0, packed = 0;
+    int fail = CDC_OK;
+    std::mutex sink_mu;  // on_pack is serialised; `stopped`: it returned a negative status
+    bool stopped = false;
+    cdc_sync_stats st{};
+
+    const cdc_packfile_row &row(const splan::Item &it) const { return S->loc.rows[it.pack][it.row]; }
+    // Wait until `counter` reaches `want`; false when the run has failed.
+    bool wait_for(const int &counter, int want)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return counter >= want || fail != CDC_OK; });
+        return fail == CDC_OK;
+    }
+    void advance(int &counter)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            ++counter;
+        }
+        cv.notify_all();
+    }
+    void abort_run(int status)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (fail == CDC_OK) fail = status;
+        }
+        cv.notify_all();
+    }
+    bool failed()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        return fail != CDC_OK;
+    }
+};
+
+// ---- reader stage ---------------------------------------------------------------
+static void reader_stage(Run &X)
+{
+    cdc_sync *S = X.S;
+    if (hipSetDevice(S->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    for (int k = 0; k < int(X.plan.batches.size()); ++k) {
+        if (!X.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
+        const splan::Batch &B = X.plan.batches[k];
+        const splan::Item *items = &X.plan.items[B.first];
+        InSlot &I = S->in[k & 1];
+        const size_t nb = size_t(B.count);
+        auto t0 = Clock::now();
+        I.eoff.assign(nb, 0);
+        I.elen.assign(nb, 0);
+        I.pre.assign(nb, CDC_OK);
+        uint64_t total = 0;
+        std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
+        for (size_t b = 0; b < nb; ++b) {
+            I.eoff[b] = total;
+            I.elen[b] = X.row(items[b]).length;
+            total += I.elen[b];
+            const cdc::Locator::Pack &P = S->loc.packs[items[b].pack];
+            if (!P.mem && !fds.count(items[b].pack)) fds[items[b].pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
+        }
+        if (!I.h.reserve(total) || !I.d.reserve(total)) {
+            for (auto &f : fds)
+                if (f.second >= 0) close(f.second);
+            return X.abort_run(CDC_E_NOMEM);
+        }
+        uint8_t *const h = I.h.as<uint8_t>();
+        parallel_for(S->o.readers, nb, [&](size_t b) {
+            const cdc::Locator::Pack &P = S->loc.packs[items[b].pack];
+            const cdc_packfile_row &R = X.row(items[b]);
+            if (P.mem) {
+                if (R.length) std::memcpy(h + I.eoff[b], P.mem + R.offset, R.length);
+                return;
+            }
+            const int fd = fds.find(items[b].pack)->second;
+            if (fd < 0 || !cdc::pread_all(fd, h + I.eoff[b], R.length, R.offset)) I.pre[b] = CDC_E_IO;
+        });
+        for (auto &f : fds)
+            if (f.second >= 0) close(f.second);
+        X.st.read_s += since(t0);
+        t0 = Clock::now();
+        if (total && (hipMemcpyAsync(I.d.data(), h, total, hipMemcpyHostToDevice, S->stream[0]) != hipSuccess ||
+                      hipStreamSynchronize(S->stream[0]) != hipSuccess))
+            return X.abort_run(CDC_E_DEVICE);
+        X.st.h2d_s += since(t0);
+        X.advance(X.uploaded);
+    }
+}
+
+// A first capacity for a batch's output: exact when the compression stays, a
+// guess (the call reports the need) when the blobs are decoded and encoded again.
+static uint64_t first_cap(const cdc_sync *S, const uint64_t *lens, size_t n)
+{
+    uint64_t total = 0, cap = 0;
+    for (size_t i = 0; i < n; ++i) total += lens[i];
+    if (S->src.compress == S->dst.compress) {
+        cap = total + (S->dst.key ? 88 * uint64_t(n) + 28 * (total / 65536) : 0);
+    } else {
+        for (size_t i = 0; i < n; ++i)
+            cap += cdc_encode_bound(lens[i] * (S->src.compress ? 4 : 1), S->dst.compress, S->dst.key != nullptr);
+    }
+    return std::max<uint64_t>(cap, 1u << 16);
+}
+
+// ---- device stage (the calling thread) --------------------------------------------
+static void device_stage(Run &X)
+{
+    cdc_sync *S = X.S;
+    std::vector<uint32_t> live;
+    std::vector<uint64_t> off, len, oo;
+    std::vector<int32_t> bst;
+    std::vector<uint8_t> sums, rnd;
+    for (int k = 0; k < int(X.plan.batches.size()); ++k) {
+        auto t0 = Clock::now();
+        if (!X.wait_for(X.uploaded, k + 1)) return;
+        X.st.device_wait_s += since(t0);
+        if (!X.wait_for(X.packed, k - 1)) return;  // batch k - 2 has left this output slot
+        const splan::Batch &B = X.plan.batches[k];
+        const splan::Item *items = &X.plan.items[B.first];
+        InSlot &I = S->in[k & 1];
+        OutSlot &O = S->out[k & 1];
+        const uint32_t nb = uint32_t(B.count);
+        t0 = Clock::now();
+        // what was read goes through Transcode; a blob that was not has failed already
+        live.clear();
+        off.clear();
+        len.clear();
+        for (uint32_t b = 0; b < nb; ++b)
+            if (I.pre[b] == CDC_OK) {
+                live.push_back(b);
+                off.push_back(I.eoff[b]);
+                len.push_back(I.elen[b]);
+            }
+        const uint32_t m = uint32_t(live.size());
+        oo.assign(size_t(m) + 1, 0);
+        bst.assign(std::max<uint32_t>(m, 1), CDC_OK);
+        if (S->o.verify) {
+            sums.resize(size_t(m) * 32 + 1);
+            for (uint32_t j = 0; j < m; ++j) std::memcpy(&sums[size_t(j) * 32], X.row(items[live[j]]).checksum, 32);
+        }
+        if (S->dst.key) {
+            rnd.resize(size_t(m) * 56 + 1);
+            const int st = random_bytes(rnd.data(), size_t(m) * 56);
+            if (st != CDC_OK) return X.abort_run(st);
+        }
+        if (m) {
+            if (!O.d.reserve(first_cap(S, len.data(), m))) return X.abort_run(CDC_E_NOMEM);
+            for (;;) {
+                const uint64_t cap = O.d.cap();
+                const int st = cdc_transcode_device_level(S->device, I.d.data(), off.data(), len.data(), m, &S->src, &S->dst,
+                                                          S->o.verify ? sums.data() : nullptr,
+                                                          S->dst.key ? rnd.data() : nullptr, O.d.as<uint8_t>(), cap,
+                                                          oo.data(), bst.data(), S->o.level, S->stream[1]);
+                if (st == CDC_E_NOSPACE && oo[m] > cap) {
+                    if (!O.d.reserve(oo[m])) return X.abort_run(CDC_E_NOMEM);
+                    continue;
+                }
+                if (st != CDC_OK) return X.abort_run(st == CDC_E_NOSPACE ? CDC_E_DEVICE : st);
+                break;
+            }
+        }
+        O.off.assign(size_t(nb) + 1, 0);
+        O.status.assign(nb, CDC_OK);
+        for (uint32_t b = 0; b < nb; ++b) O.status[b] = I.pre[b];
+        tplan::spread_results(live.data(), m, oo.data(), bst.data(), nb, O.off.data(), O.status.data());
+        X.st.transcode_s += since(t0);
+        for (uint32_t b = 0; b < nb; ++b) {
+            ++X.st.blobs;
+            X.st.bytes_in += I.elen[b];
+            if (O.status[b] != CDC_OK)
+                ++X.st.failed;
+            else
+                X.st.bytes_out += O.off[b + 1] - O.off[b];
+        }
+        ++X.st.batches;
+        X.advance(X.consumed);
+        X.advance(X.transcoded);
+    }
+}
+
+// ---- packer stage -------------------------------------------------------------------
+// The packer's packfile, serialised in place, to PutPackfile (on_pack).
+static void sink(Run &X, cdc_packer *p)
+{
+    const uint8_t *data = nullptr;
+    uint64_t len = 0;
+    int st = cdc::packer_seal(p, X.S->o.timestamp, &data, &len);
+    if (st == CDC_OK) {
+        std::lock_guard<std::mutex> lk(X.sink_mu);
+        if (!X.stopped) {
+            ++X.st.packfiles;
+            X.st.packed_bytes += len;
+            const auto t0 = Clock::now();
+            st = X.on_pack(X.ctx, data, len);
+            X.st.callback_s += since(t0);
+            if (st < 0) X.stopped = true;
+        }
+    }
+    cdc_packer_reset(p);
+    if (st < 0) X.abort_run(st);
+}
+
+static void packer_stage(Run &X)
+{
+    cdc_sync *S = X.S;
+    if (hipSetDevice(S->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    const uint32_t np = uint32_t(S->packers.size());
+    std::vector<uint32_t> bounds;
+    for (int k = 0; k < int(X.plan.batches.size()); ++k) {
+        if (!X.wait_for(X.transcoded, k + 1)) return;
+        const splan::Batch &B = X.plan.batches[k];
+        const splan::Item *items = &X.plan.items[B.first];
+        OutSlot &O = S->out[k & 1];
+        const uint32_t nb = uint32_t(B.count);
+        const uint64_t total = O.off[nb];
+        auto t0 = Clock::now();
+        if (!O.h.reserve(total)) return X.abort_run(CDC_E_NOMEM);
+        const uint8_t *const image = O.h.as<uint8_t>();
+        if (total && (hipMemcpyAsync(O.h.data(), O.d.data(), total, hipMemcpyDeviceToHost, S->stream[2]) != hipSuccess ||
+                      hipStreamSynchronize(S->stream[2]) != hipSuccess))
+            return X.abort_run(CDC_E_DEVICE);
+        X.st.d2h_s += since(t0);
+        if (X.on_fail) {
+            t0 = Clock::now();
+            for (uint32_t b = 0; b < nb; ++b)
+                if (O.status[b] != CDC_OK) {
+                    const cdc_packfile_row &R = X.row(items[b]);
+                    X.on_fail(X.ctx, R.type, R.checksum, O.status[b]);
+                }
+            X.st.callback_s += since(t0);
+        }
+        t0 = Clock::now();
+        const double cb0 = X.st.callback_s;  // no packer runs outside the step below
+        splan::split(O.off.data(), nb, np, bounds);
+        parallel_for(int(np), np, [&](size_t p) {
+            cdc_packer *pk = S->packers[p];
+            for (uint32_t b = bounds[p]; b < bounds[p + 1]; ++b) {
+                if (O.status[b] != CDC_OK) continue;
+                if (X.failed()) return;
+                const cdc_packfile_row &R = X.row(items[b]);
+                const int st = cdc_packer_add_blob(pk, R.type, R.checksum, image + O.off[b], O.off[b + 1] - O.off[b]);
+                if (st < 0) return X.abort_run(st);
+                if (st == 1) sink(X, pk);  // Size() > MaxSize: packerJob flushes (snapshot/snapshot.go:71)
+            }
+        });
+        X.st.pack_s += since(t0) - (X.st.callback_s - cb0);
+        X.advance(X.packed);
+    }
+    // the last, partial packfiles
+    const auto t0 = Clock::now();
+    const double cb0 = X.st.callback_s;
+    for (cdc_packer *pk : S->packers)
+        if (cdc_packer_count(pk) && !X.failed()) sink(X, pk);
+    X.st.pack_s += since(t0) - (X.st.callback_s - cb0);
+}
+
+static int run_sync(cdc_sync *S, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack,
+                    cdc_sync_blob_fn on_fail, void *ctx, cdc_sync_stats *stats)
+{
+    const auto w0 = Clock::now();
+    Run X{};
+    X.S = S;
+    X.on_pack = on_pack;
+    X.on_fail = on_fail;
+    X.ctx = ctx;
+    std::vector<splan::Pack> packs;
+    for (const auto &rows : S->loc.rows) packs.push_back(splan::Pack{rows.data(), rows.size()});
+    splan::plan(packs.data(), packs.size(), S->known.data(), S->o.nknown, wanted, nwanted, S->o.batch_bytes, X.plan);
+    X.st.skipped = X.plan.skipped;
+    X.st.path = int32_t(tplan::choose_path(S->src.compress, S->src.key != nullptr, S->dst.compress, S->dst.key != nullptr));
+    for (cdc_packer *pk : S->packers) cdc_packer_reset(pk);
+    if (!X.plan.batches.empty()) {
+        if (hipSetDevice(S->device) != hipSuccess) return CDC_E_DEVICE;
+        auto guarded = [&X](void (*stage)(Run &)) {
+            try {
+                stage(X);
+            } catch (...) {
+                X.abort_run(CDC_E_NOMEM);
+            }
+        };
+        std::thread reader(guarded, reader_stage);
+        std::thread packer(guarded, packer_stage);
+        guarded(device_stage);
+        reader.join();
+        packer.join();
+    }
+    for (cdc_packer *pk : S->packers) cdc_packer_reset(pk);  // what a run that broke off left behind
+    X.st.wall_s = since(w0);
+    if (stats) {
+        X.st.struct_size = uint32_t(std::min<size_t>(stats->struct_size, sizeof(X.st)));
+        std::memcpy(stats, &X.st, X.st.struct_size);
+    }
+    return X.fail;
+}
+
+}  // namespace
+
+extern "C" {
+
+void cdc_sync_default_opts(cdc_sync_opts *out)
+{
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->verify = 1;
+}
+
+int cdc_sync_new(int device, const cdc_sync_opts *opts, cdc_sync **out)
+{
+    if (!opts || !out) return CDC_E_INVALID;
+    *out = nullptr;
+    if (opts->struct_size != sizeof(*opts) || device < 0 || device >= cdc::kMaxDevices || !compress_ok(opts->src.compress) ||
+        !compress_ok(opts->dst.compress) || !cdc::level_ok(opts->level) || opts->readers < 0 || opts->readers > 256 ||
+        opts->packers < 0 || opts->packers > 256 || (opts->nknown && !opts->known) ||
+        opts->nknown > SIZE_MAX / splan::kKeyBytes || !splan::sorted33(opts->known, opts->nknown))
+        return CDC_E_INVALID;
+    if (!cdc::device_count_initialised()) return CDC_E_NOT_INIT;
+    auto *s = new (std::nothrow) cdc_sync();
+    if (!s) return CDC_E_NOMEM;
+    try {
+        s->device = device;
+        s->o = *opts;
+        if (opts->src.key) s->skey.assign(opts->src.key, opts->src.key + 32);
+        if (opts->dst.key) s->dkey.assign(opts->dst.key, opts->dst.key + 32);
+        if (opts->nknown) s->known.assign(opts->known, opts->known + splan::kKeyBytes * opts->nknown);
+        s->src = cdc_codec{opts->src.compress, s->skey.empty() ? nullptr : s->skey.data()};
+        s->dst = cdc_codec{opts->dst.compress, s->dkey.empty() ? nullptr : s->dkey.data()};
+        s->o.src.key = s->o.dst.key = s->o.known = nullptr;
+        if (!s->o.readers) s->o.readers = 8;
+        if (!s->o.packers) s->o.packers = 8;
+        if (!s->o.batch_bytes) s->o.batch_bytes = 64ull << 20;
+        s->loc.keep_rows = true;
+        for (int p = 0; p < s->o.packers; ++p) {
+            cdc_packer *pk = nullptr;
+            if (cdc_packer_new(s->o.packfile_max, &pk) != CDC_OK) throw std::bad_alloc();
+            s->packers.push_back(pk);
+        }
+    } catch (...) {
+        cdc_sync_free(s);
+        return CDC_E_NOMEM;
+    }
+    bool ok = hipSetDevice(device) == hipSuccess;
+    for (int i = 0; i < 3; ++i) ok = ok && hipStreamCreateWithFlags(&s->stream[i], hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        cdc_sync_free(s);
+        return CDC_E_DEVICE;
+    }
+    *out = s;
+    return CDC_OK;
+}
+
+int cdc_sync_add_packfile(cdc_sync *s, const uint8_t *bytes, uint64_t len)
+{
+    if (!s || (!bytes && len)) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(s->run_mu);
+    try {
+        return s->loc.add_memory(bytes, len);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_sync_add_packfile_path(cdc_sync *s, const char *path)
+{
+    if (!s || !path) return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(s->run_mu);
+    try {
+        return s->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack, cdc_sync_blob_fn on_fail,
+                 void *ctx, cdc_sync_stats *stats)
+{
+    if (!s || !on_pack || (stats && stats->struct_size < 8) || (wanted && !splan::sorted33(wanted, nwanted)))
+        return CDC_E_INVALID;
+    std::lock_guard<std::mutex> lk(s->run_mu);
+    try {
+        return run_sync(s, wanted, nwanted, on_pack, on_fail, ctx, stats);
+    } catch (const std::bad_alloc &) {
+        return CDC_E_NOMEM;
+    }
+}
+
+void cdc_sync_free(cdc_sync *s)
+{
+    if (!s) return;
+    bool any = false;
+    for (auto &st : s->stream) any = any || st;
+    if (any) {
+        (void)hipSetDevice(s->device);
+        for (auto &st : s->stream)
+            if (st) {
+                (void)hipStreamSynchronize(st);
+                (void)hipStreamDestroy(st);
+            }
+    }
+    for (cdc_packer *pk : s->packers) cdc_packer_free(pk);
+    if (!s->skey.empty()) std::memset(s->skey.data(), 0, s->skey.size());
+    if (!s->dkey.empty()) std::memset(s->dkey.data(), 0, s->dkey.size());
+    delete s;  // the slots' buffers go with it, the streams drained above
+}
+
+}  // extern "C"

@@ -486,7 +486,8 @@ def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", kn
 from .restore import RestoreSession, SnapshotFile, read_ranges, restore_files  # noqa: E402 - the read path, next to backup_files
 from .check import CheckSession, check_files  # noqa: E402 - and the check of what was written
 from .diff import DiffSession, diff_files  # noqa: E402 - and the diff of two versions of it
+from .sync import SyncPipeline, sync_packfiles  # noqa: E402 - and its packfiles as another repository's
 
 __all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
            "RestoreSession", "restore_files", "read_ranges", "SnapshotFile", "CheckSession", "check_files", "DiffSession",
-           "diff_files"]
+           "diff_files", "SyncPipeline", "sync_packfiles"]

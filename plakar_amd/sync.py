@@ -8,12 +8,15 @@ does the first two for a batch without the plaintext leaving the device, and,
 when both repositories name the same compression, without inflating at all:
 only the GCM envelope changes (the re-key; with both keys set the plaintext
 never exists in device memory either).  SyncSession is synchronize()'s loop over
-source packfiles.  Every device call goes through the C ABI
-(cdc_transcode_device, cdc_transcode_size; cdc_packfile_index and cdc_packer_*
-through restore.packfile_index and packer.Packer).
+source packfiles, one stage after the other, in Python.  SyncPipeline is the
+same loop behind the C ABI (cdc_sync_*): batch k + 1 is gathered and uploaded
+while batch k is transcoded and batch k - 1 is downloaded and packed, and the
+blobs are never copied in Python.  Every device call goes through the C ABI
+(cdc_transcode_device, cdc_transcode_size, cdc_sync_*; cdc_packfile_index and
+cdc_packer_* through restore.packfile_index and packer.Packer).
 
 Out of scope: the PutPackfile stored form of a packfile (restore does not read
-it either) and the snapshot, state and header records."""
+it either), the snapshot, state and header records, and more than one device."""
 import ctypes
 import os
 import time
@@ -265,5 +268,135 @@ class SyncSession:
         return packfiles, failures, stats
 
 
-__all__ = ["transcode_device", "transcode_blobs", "transcode_size", "path_of", "SyncSession", "TranscodeError",
-           "DEFAULT_BATCH_BYTES", "PATHS"]
+def _records(pairs):
+    """(type, checksum) pairs as cdc_sync's 33-byte records, sorted ascending."""
+    recs = sorted(bytes([int(t)]) + bytes(c) for t, c in pairs)
+    if any(len(r) != 33 for r in recs):
+        raise ValueError("a checksum is 32 bytes (SHA-256)")
+    return b"".join(recs), len(recs)
+
+
+class SyncPipeline:
+    """A native sync context (cdc_sync_new): SyncSession's loop as a pipeline
+    whose reads, uploads, downloads and packing overlap the device work.
+
+    The arguments are SyncSession's, and known, wanted and failures are keyed
+    the same way ((type, checksum) tuples).  readers and packers: threads (0: 8
+    each).  With packers=1 the packfiles are SyncSession's, row for row; with
+    more, every packfile still holds its rows in source order.  timestamp=None
+    takes the time of the call, once, for every packfile of the context."""
+
+    def __init__(self, src_key=None, src_compression="LZ4", dst_key=None, dst_compression="LZ4", verify=True,
+                 known=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0, level=0,
+                 readers=0, packers=0):
+        self._h = None
+        self._keep = []  # packfile bytes the context reads from until it is freed
+        level = _lib.level_code(level)
+        self.src, self.dst = (src_key, src_compression), (dst_key, dst_compression)
+        (skey, scomp), (dkey, dcomp) = _codec(self.src), _codec(self.dst)  # ValueError for a bad key or name
+        self.path = path_of(self.src, self.dst)
+        recs, nrecs = _records(known if known is not None else ())
+        ensure_init()
+        o = _lib.cdc_sync_opts()
+        lib().cdc_sync_default_opts(ctypes.byref(o))
+        o.src, o.dst = _lib.cdc_codec(scomp, skey), _lib.cdc_codec(dcomp, dkey)
+        o.verify, o.level = int(bool(verify)), level
+        o.packfile_max = 0 if max_size is None else int(max_size)
+        o.batch_bytes = max(int(batch_bytes), 1)
+        o.readers, o.packers = int(readers), int(packers)
+        o.timestamp = time.time_ns() if timestamp is None else int(timestamp)
+        kbuf = ctypes.create_string_buffer(recs, max(len(recs), 1))
+        o.known, o.nknown = (ctypes.cast(kbuf, ctypes.c_void_p) if nrecs else None), nrecs
+        h = ctypes.c_void_p()
+        _lib.check(lib().cdc_sync_new(int(device), ctypes.byref(o), ctypes.byref(h)), "cdc_sync_new")
+        self._h = h
+
+    def add_packfile(self, packfile):
+        """Register a source packfile: bytes (kept alive by the context) or a
+        path, whose blobs are read during a run.  Raises CdcError(CDC_E_CORRUPT)
+        for a malformed one."""
+        if not self._h:
+            raise ValueError("pipeline closed")
+        if isinstance(packfile, (str, os.PathLike)):
+            _lib.check(lib().cdc_sync_add_packfile_path(self._h, os.fsencode(packfile)), "cdc_sync_add_packfile_path")
+            return
+        buf = bytes(packfile)
+        _lib.check(lib().cdc_sync_add_packfile(self._h, buf, len(buf)), "cdc_sync_add_packfile")
+        self._keep.append(buf)
+
+    def run(self, wanted=None, on_pack=None):
+        """One sync (cdc_sync_run).  Returns (packfiles, failures, stats) as
+        SyncSession.run does; stats holds the fields of cdc_sync_stats, `path`
+        as its name in PATHS.  on_pack: None, or a callable that is handed
+        each packfile (bytes) instead of the returned list and whose negative
+        return value stops the run (CdcError with that status)."""
+        if not self._h:
+            raise ValueError("pipeline closed")
+        packfiles, failures, errors = [], {}, []
+
+        def pack_cb(_ctx, data, n):
+            try:
+                raw = ctypes.string_at(data, n)
+                if on_pack is None:
+                    packfiles.append(raw)
+                    return 0
+                r = on_pack(raw)
+                return 0 if r is None else int(r)
+            except Exception as e:  # noqa: BLE001 - re-raised after the call
+                errors.append(e)
+                return _lib.CDC_E_IO
+
+        def fail_cb(_ctx, typ, checksum, status):
+            try:
+                failures[(int(typ), ctypes.string_at(checksum, 32))] = int(status)
+            except Exception as e:  # noqa: BLE001 - re-raised after the call
+                errors.append(e)
+
+        wrecs, nw = (None, 0) if wanted is None else _records(wanted)
+        wbuf = None if wrecs is None else ctypes.create_string_buffer(wrecs, max(len(wrecs), 1))
+        st = _lib.cdc_sync_stats()
+        st.struct_size = ctypes.sizeof(st)
+        pcb, fcb = _lib.BACKUP_PACK_FN(pack_cb), _lib.SYNC_BLOB_FN(fail_cb)
+        rc = lib().cdc_sync_run(self._h, None if wbuf is None else ctypes.cast(wbuf, ctypes.c_void_p), nw, pcb, fcb,
+                                None, ctypes.byref(st))
+        if errors:
+            raise errors[0]
+        _lib.check(rc, "cdc_sync_run")
+        stats = {name: getattr(st, name) for name, _ in _lib.cdc_sync_stats._fields_ if name != "struct_size"}
+        stats["path"] = PATHS[stats["path"]]
+        return packfiles, failures, stats
+
+    def close(self):
+        if self._h:
+            lib().cdc_sync_free(self._h)
+            self._h = None
+            self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def sync_packfiles(packfiles, src_key=None, src_compression="LZ4", dst_key=None, dst_compression="LZ4", verify=True,
+                   known=None, wanted=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0,
+                   level=0, readers=0, packers=0):
+    """One sync through the native pipeline (a SyncPipeline for this call
+    only): packfiles is a list of serialised packfiles (bytes) and/or paths.
+    Returns (packfiles, failures, stats) as SyncPipeline.run."""
+    with SyncPipeline(src_key, src_compression, dst_key, dst_compression, verify, known, max_size, batch_bytes,
+                      timestamp, device, level, readers, packers) as s:
+        for p in packfiles:
+            s.add_packfile(p)
+        return s.run(wanted)
+
+
+__all__ = ["transcode_device", "transcode_blobs", "transcode_size", "path_of", "SyncSession", "SyncPipeline",
+           "sync_packfiles", "TranscodeError", "DEFAULT_BATCH_BYTES", "PATHS"]

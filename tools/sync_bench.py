@@ -12,6 +12,17 @@ settings are timed with hipEvents, both routes in the same process, alternated:
 One JSON line per set and setting: every repetition's seconds for both routes,
 their medians and spreads ((max - min) / median), GiB/s of stored bytes and of
 plaintext, and chain over transcode (above 1: the transcode is faster).
+
+    python tools/sync_bench.py --pipeline [--sets c1,c3,text] [--size-mib 128] [--reps 5] [--batch-mib 16]
+
+times whole syncs of packfiles instead: each set's chunks are stored once under
+key A / LZ4 in packfiles, and per leg (A -> B re-key with and without the
+check, LZ4 -> GZIP re-encode) sync.SyncSession.run() and the native
+sync.SyncPipeline.run() are alternated in one process on the same packfiles
+and the same batch size.  One JSON line per set and leg, and all of them in
+profiles/sync_bench_pipeline.json: both walls with medians and spreads, the
+native run's stage seconds, the overlap it achieved (the sum of the stage
+walls over wall_s) and device_wait_s.
 """
 import argparse
 import json
@@ -28,15 +39,137 @@ SETTINGS = {"rekey-lz4": ("LZ4", "LZ4"), "rekey-gzip": ("GZIP", "GZIP"), "lz4-to
             "gzip-to-lz4": ("GZIP", "LZ4")}
 
 
+# --pipeline: leg -> (destination compression, verify)
+LEGS = {"rekey-verify": ("LZ4", True), "rekey": ("LZ4", False), "lz4-to-gzip": ("GZIP", True)}
+STAGES = ("read_s", "h2d_s", "transcode_s", "d2h_s", "pack_s", "callback_s")
+SESSION_STAGES = ("gather_s", "h2d_s", "transcode_s", "d2h_s", "pack_s")
+
+
+def pipeline(a):
+    """Whole syncs of packfiles: SyncSession.run() against SyncPipeline.run()."""
+    import hashlib
+    import time
+
+    import numpy as np
+    import torch
+
+    import bench
+    from decode_bench import text_like
+    from plakar_amd import _lib, chunkers, device, encode, packer, restore, sync
+    _lib.ensure_init()
+    dev = torch.device("cuda", 0)
+    key_a, key_b = os.urandom(32), os.urandom(32)
+    opts = chunkers.ChunkerOpts(65536, 1 << 20, 4 << 20)
+    size = a.size_mib << 20
+    batch = a.batch_mib << 20
+    records = []
+    for name in a.sets.split(","):
+        if name == "text":
+            buf = torch.from_numpy(np.frombuffer(text_like(np, size), dtype=np.uint8).copy()).to(dev)
+        else:
+            buf = bench.make_buffers(torch, bench.WORKLOADS[name], 0, dev, size)[0]
+        b = device.DeviceBatch([buf], opts)
+        b.launch()
+        cuts, _ = b.results()
+        c = cuts[0].cpu().numpy().astype(np.int64)
+        offs, lens = c[:, 0], c[:, 1]
+        del b
+        # the source repository: every distinct chunk once, under key A / LZ4, in packfiles of the default size
+        cap = sum(encode.encode_bound(int(x), True, True) for x in lens)
+        enc = torch.empty(cap, dtype=torch.uint8, device=dev)
+        oo = encode.encode_device(buf, offs, lens, enc, key=key_a, compress=True)
+        stored = enc[:int(oo[-1])].cpu().numpy()
+        plain = buf.cpu().numpy()
+        del enc, buf
+        packs, seen = [], set()
+        pk = packer.Packer(timestamp=1)
+        for i in range(len(lens)):
+            digest = hashlib.sha256(plain[int(offs[i]):int(offs[i]) + int(lens[i])]).digest()
+            if digest in seen:
+                continue
+            seen.add(digest)
+            if pk.AddBlob(1, digest, stored[int(oo[i]):int(oo[i + 1])]):
+                packs.append(pk.Serialize())
+                pk.Reset()
+        if pk.Count():
+            packs.append(pk.Serialize())
+        pk.close()
+        nblobs, sbytes, pbytes = len(seen), sum(len(p) for p in packs), int(lens.sum())
+        del stored, plain
+        for leg in a.legs.split(","):
+            dc, verify = LEGS[leg]
+            kw = dict(src_key=key_a, src_compression="LZ4", dst_key=key_b, dst_compression=dc, verify=verify,
+                      batch_bytes=batch, timestamp=2)
+            session = sync.SyncSession(**kw)
+            native = sync.SyncPipeline(packers=a.packers, **kw)
+            for p in packs:
+                session.add_packfile(p)
+                native.add_packfile(p)
+
+            def timed(run):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = run()
+                return out, time.perf_counter() - t0
+
+            session.run(), native.run()  # warm: workspace growth, tables, the slots' buffers
+            ss, ns, nstats, sstats = [], [], [], []
+            for _ in range(a.reps):  # alternated, so both routes see the same neighbours
+                (spacks, sfail, sst), s = timed(session.run)
+                (npacks, nfail, nst), n = timed(native.run)
+                ss.append(s)
+                ns.append(n)
+                sstats.append(sst)
+                nstats.append(nst)
+            rows = lambda ps: sorted((t, c, ln) for p in ps for t, c, _, ln in restore.packfile_index(p)[1])  # noqa: E731
+            same = sfail == nfail == {} and rows(spacks) == rows(npacks)
+            native.close()
+            sm, nm = statistics.median(ss), statistics.median(ns)
+            s_spread, n_spread = (max(ss) - min(ss)) / sm, (max(ns) - min(ns)) / nm
+            stage = {k: statistics.mean(st[k] for st in nstats) for k in STAGES + ("device_wait_s", "wall_s")}
+            sstage = {k: statistics.mean(st[k] for st in sstats) for k in SESSION_STAGES}
+            rec = dict(
+                set=name, leg=leg, path=nst["path"], verify=verify, blobs=nblobs, batches=int(nst["batches"]),
+                source_packfiles=len(packs), packfiles=int(nst["packfiles"]), plain_bytes=pbytes, stored_bytes=sbytes,
+                bytes_in=int(nst["bytes_in"]), bytes_out=int(nst["bytes_out"]), batch_bytes=batch, packers=a.packers,
+                size_mib=a.size_mib, reps=a.reps, same_rows_as_session=bool(same),
+                session_wall_s=ss, native_wall_s=ns, session_median_s=sm, native_median_s=nm,
+                session_spread=s_spread, native_spread=n_spread, session_over_native=sm / nm,
+                session_gibs=nst["bytes_in"] / sm / 2**30, native_gibs=nst["bytes_in"] / nm / 2**30,
+                # the expectation: native no longer than the session by more than the larger of the two spreads
+                expectation_met=bool(nm - sm <= max(s_spread * sm, n_spread * nm)),
+                native_stage_s=stage, session_stage_s=sstage,
+                bounding_stage=max(STAGES, key=lambda k: stage[k]),
+                overlap=sum(stage[k] for k in STAGES) / stage["wall_s"], device_wait_s=stage["device_wait_s"])
+            records.append(rec)
+            print(json.dumps(rec), flush=True)
+        del packs
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(dict(tool="tools/sync_bench.py --pipeline", records=records), f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="c1,c3,text")
     ap.add_argument("--size-mib", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--settings", default=",".join(SETTINGS))
+    ap.add_argument("--pipeline", action="store_true", help="whole syncs: SyncSession against the native pipeline")
+    ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--batch-mib", type=int, default=16, help="--pipeline: stored bytes per batch, both routes")
+    ap.add_argument("--packers", type=int, default=0, help="--pipeline: the native run's packer threads (0: 8)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sync_bench_pipeline.json"),
+                    help="--pipeline: where the records go ('' for nowhere)")
     a = ap.parse_args()
     if a.reps < 3:
         ap.error("at least 3 repetitions: the spread is part of the result")
+    if a.pipeline:
+        if a.reps < 5:
+            ap.error("--pipeline: at least 5 repetitions of each route")
+        return pipeline(a)
 
     import numpy as np
     import torch
