@@ -635,6 +635,15 @@ void cdc_backup_free(cdc_backup *b);
  * smaller LZ4 or GZIP blobs.  A run in progress keeps the level it began with.
  * cdc_backup_run has no session: cdc_backup_run_level takes the level. */
 int cdc_backup_set_level(cdc_backup *b, int level);
+/* The form of the packfiles on_pack receives in later cdc_backup_files calls:
+ * CDC_PACKFILE_PLAIN (0, the default) or CDC_PACKFILE_STORED (1), the bytes
+ * repository.PutPackfile stores (the stored form, below): a packer seals its
+ * packfile as before, then its index and footer go through one Encode call at
+ * CDC_LEVEL_FAST with the session's compress and key, under the lock that
+ * serialises on_pack.  That Encode uses the workspace of the pipeline's first
+ * encoder thread and waits for a batch's Encode there.  Any
+ * other form is CDC_E_INVALID.  A run in progress keeps its form. */
+int cdc_backup_set_packfile_form(cdc_backup *b, int form);
 /* new + files + free in one call. */
 int cdc_backup_run(int device, const char *const *paths, int n, const cdc_backup_opts *opts,
                    cdc_backup_file_fn on_file, cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats);
@@ -662,7 +671,8 @@ int cdc_backup_run_level(int device, const char *const *paths, int n, const cdc_
  * 100, an index that is not 41 * count bytes, an entry whose offset + length
  * passes the index offset, or an index whose SHA-256 (cdc_sha256) is not the
  * footer's.  Host only; needs no cdc_init.  The PutPackfile form, whose index
- * and footer went through Encode (snapshot/snapshot.go:249-267), is not read. */
+ * and footer went through Encode (snapshot/snapshot.go:249-267), is
+ * CDC_E_CORRUPT here: cdc_packfile_index_stored reads it. */
 typedef struct cdc_packfile_footer {
     uint32_t version;       /* 100 */
     uint32_t count;
@@ -679,6 +689,58 @@ typedef struct cdc_packfile_row {
 } cdc_packfile_row;
 int cdc_packfile_index(const uint8_t *bytes, uint64_t len, cdc_packfile_footer *footer, cdc_packfile_row *rows,
                        uint64_t cap, uint64_t *needed);
+
+/* ---- the stored form: what a repository keeps -------------------------------------
+ * snapshot.PutPackfile (snapshot/snapshot.go:232-267) stores, and the fs
+ * backend writes unchanged (storage/backends/fs/fs.go:270-292),
+ *     data || Encode(index) || Encode(footer) || u32le version || u8 len(Encode(footer))
+ * with Encode the repository's compression, then its AES-256-GCM stream
+ * (repository/repository.go:212-262), as for every blob.  Read back
+ * (cmd/plakar/subcommands/info/info.go:387-426) for a file of len bytes:
+ * L = bytes[len - 1], version = u32le(bytes[len - 5 .. len - 1)), the encoded
+ * footer is bytes[len - 5 - L .. len - 5) and decodes to the 52-byte footer,
+ * the encoded index is bytes[footer.index_offset .. len - 5 - L) and decodes to
+ * 41 * footer.count bytes whose SHA-256 is footer.index_checksum.  The blobs
+ * sit at the offsets the rows give, as in the plain form.
+ * A source of a cdc_*_add_packfiles call names its form: */
+#define CDC_PACKFILE_PLAIN  0   /* (*PackFile).Serialize: cdc_packer_serialize's form, the default everywhere */
+#define CDC_PACKFILE_STORED 1   /* snapshot.PutPackfile: what a repository keeps */
+#define CDC_PACKFILE_ROWS   2   /* the caller supplies the index (the repository state's rows,
+                                 * state.GetSubpartForBlob): nothing of the file's tail is read or decoded */
+typedef struct cdc_packfile_src {
+    const uint8_t *bytes;         /* memory form (lifetime as cdc_restore_add_packfile), or NULL */
+    uint64_t len;
+    const char *path;             /* path form, when bytes == NULL */
+    int form;                     /* CDC_PACKFILE_* */
+    const cdc_packfile_row *rows; /* CDC_PACKFILE_ROWS only; copied */
+    uint64_t nrows;
+} cdc_packfile_src;
+
+/* cdc_packfile_index for one stored packfile in host memory: the two tails go
+ * through cdc_decode_device on `device` (compress, key: as there), the rows
+ * are checked and hashed on the host.  footer, rows, cap, *needed and
+ * CDC_E_NOSPACE as cdc_packfile_index.  CDC_E_CORRUPT: fewer than 5 bytes, a
+ * last byte of 0 in a repository with a key or a compression, a last byte
+ * that passes the file, a trailer or footer version other than 100, a footer
+ * that does not decode to 52 bytes, an index offset past the encoded footer, a
+ * count the encoded index cannot inflate to (checked before anything is sized
+ * from it), an index that does not decode to 41 * count bytes, a row past the
+ * index offset, an index checksum mismatch, and any Decode failure but
+ * CDC_E_AUTH, which is a GCM tag of the footer or the index.  A plain-form
+ * packfile is CDC_E_CORRUPT or CDC_E_AUTH. */
+int cdc_packfile_index_stored(int device, const uint8_t *bytes, uint64_t len, int compress, const uint8_t *key,
+                              cdc_packfile_footer *footer, cdc_packfile_row *rows, uint64_t cap, uint64_t *needed);
+
+/* The packer's packfile in the stored form: its data section, then its index
+ * and its footer through one cdc_encode_device_level at CDC_LEVEL_FAST
+ * (compress, key: as there; random: 112 bytes, the index's 56 then the
+ * footer's 56, or NULL: drawn with getrandom(2)), then the trailer.
+ * CDC_E_NOSPACE with *len set when cap is too small; cdc_packer_stored_bound
+ * is enough.  CDC_E_UNSUPPORTED when the encoded footer takes 256 bytes or
+ * more (its length field is one byte; no configuration here reaches 200). */
+uint64_t cdc_packer_stored_bound(const cdc_packer *p, int compress, int encrypt);
+int cdc_packer_serialize_stored(const cdc_packer *p, int64_t timestamp, int device, int compress, const uint8_t *key,
+                                const uint8_t *random, uint8_t *out, uint64_t cap, uint64_t *len);
 
 /* The copy loop of vfilep.go:58-122 (`copy(p, data[...])` per chunk) for a
  * batch, on the device: for each of n segments (host arrays), d_dst[dst_off[i],
@@ -747,6 +809,23 @@ int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out)
  * CDC_E_CORRUPT, CDC_E_IO (the path form), CDC_E_NOMEM. */
 int cdc_restore_add_packfile(cdc_restore *r, const uint8_t *bytes, uint64_t len);
 int cdc_restore_add_packfile_path(cdc_restore *r, const char *path);
+/* n packfiles in one call, each in the form it names (cdc_packfile_src above;
+ * one call may mix forms).  The stored ones cost two cdc_decode_device calls
+ * together, one over their encoded footers and one over their encoded indexes,
+ * whatever their number (a repository holds one packfile per 20 MiB); the
+ * context's own compress and key decode them (for cdc_sync: the source's).
+ * Plain sources go through cdc_restore_add_packfile[_path].  A
+ * CDC_PACKFILE_ROWS source enters the caller's rows for a file whose length is
+ * `len` or fstat(2)'s; nothing else of the file is read now.
+ * Returns CDC_OK whenever the call ran; status[i] (n) is CDC_OK, CDC_E_IO,
+ * CDC_E_AUTH (a GCM tag of the footer or the index) or CDC_E_CORRUPT (as
+ * cdc_packfile_index_stored; a row of a rows source past the file's length).
+ * Only sources with CDC_OK are entered, in source order: a checksum already
+ * there keeps its first location.  CDC_E_INVALID before the device is
+ * touched: NULL arguments, an unknown form, CDC_PACKFILE_ROWS without rows,
+ * neither bytes nor path, a call during a run of the context.  One each for
+ * restore (and cdc_restore_ranges), check, diff, archive and sync. */
+int cdc_restore_add_packfiles(cdc_restore *r, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);
 /* Restore n files from their chunk lists (what cdc_backup_files' on_file
  * delivered: Object.Chunks).  Per batch of at most batch_bytes of output (a
  * larger file goes in pieces cut on chunk boundaries): reader threads gather
@@ -917,6 +996,7 @@ typedef struct cdc_check cdc_check;
 int cdc_check_new(int device, const cdc_check_opts *opts, cdc_check **out);
 int cdc_check_add_packfile(cdc_check *c, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
 int cdc_check_add_packfile_path(cdc_check *c, const char *path);
+int cdc_check_add_packfiles(cdc_check *c, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);  /* as cdc_restore_add_packfiles */
 /* Check n files from their chunk lists and object checksums.  Per batch of at
  * most batch_bytes of file bytes (restore's plan): reader threads gather the
  * batch's distinct encoded blobs, one upload, one Decode with SHA-256 and
@@ -1113,6 +1193,7 @@ typedef struct cdc_diff cdc_diff;
 int cdc_diff_new(int device, const cdc_diff_opts *opts, cdc_diff **out);
 int cdc_diff_add_packfile(cdc_diff *d, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
 int cdc_diff_add_packfile_path(cdc_diff *d, const char *path);
+int cdc_diff_add_packfiles(cdc_diff *d, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);  /* as cdc_restore_add_packfiles */
 /* The unified diffs of n pairs.  A pair whose two object checksums are given
  * and equal, or whose chunk lists are equal, is identical with no device work
  * (diff.go:156).  The others go in batches of whole pairs of at most
@@ -1197,6 +1278,7 @@ typedef struct cdc_sync cdc_sync;
 int cdc_sync_new(int device, const cdc_sync_opts *opts, cdc_sync **out);
 int cdc_sync_add_packfile(cdc_sync *s, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
 int cdc_sync_add_packfile_path(cdc_sync *s, const char *path);
+int cdc_sync_add_packfiles(cdc_sync *s, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);  /* as cdc_restore_add_packfiles */
 /* One sync of the registered packfiles.  Three stages, batch k + 1 read and
  * uploaded while batch k is on the device and batch k - 1 is downloaded and
  * packed:
@@ -1227,10 +1309,13 @@ int cdc_sync_add_packfile_path(cdc_sync *s, const char *path);
  * run's taken-set starts empty.  Returns CDC_OK, or the run's own first
  * failure (a device error, on_pack's status); CDC_E_INVALID before the device
  * is touched: NULL s or on_pack, wanted unsorted, stats->struct_size < 8.
- * Out of scope: the PutPackfile stored form on either side, the snapshot,
- * state and header records, more than one device. */
+ * Out of scope: the snapshot, state and header records, more than one device. */
 int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack,
                  cdc_sync_blob_fn on_fail, void *ctx, cdc_sync_stats *stats);
+/* The destination's packfile form in later runs (CDC_PACKFILE_PLAIN, the
+ * default, or CDC_PACKFILE_STORED; as cdc_backup_set_packfile_form, with the
+ * destination's codec).  The source's form comes with each source. */
+int cdc_sync_set_packfile_form(cdc_sync *s, int form);
 void cdc_sync_free(cdc_sync *s);
 
 /* ---- archive: a snapshot's entries as one tar or tar.gz stream -------------------
@@ -1300,6 +1385,7 @@ typedef struct cdc_archive cdc_archive;
 int cdc_archive_new(int device, const cdc_archive_opts *opts, cdc_archive **out);
 int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
 int cdc_archive_add_packfile_path(cdc_archive *a, const char *path);
+int cdc_archive_add_packfiles(cdc_archive *a, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);  /* as cdc_restore_add_packfiles */
 int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path,
                     cdc_archive_data_fn on_data, cdc_archive_entry_fn on_entry, void *ctx, cdc_archive_stats *stats);
 void cdc_archive_free(cdc_archive *a);

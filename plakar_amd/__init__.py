@@ -17,9 +17,11 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
                            line_ids_device, diff_script, diff_emit_device)
     plakar_amd.sync        blobs of one repository as blobs of another, on the device: re-key and
                            re-encode (transcode_device), synchronize()'s loop over packfiles (SyncSession)
+    plakar_amd.stored      the form a repository keeps its packfiles in (snapshot.PutPackfile): many
+                           packfiles registered in one call (add_packfiles on every session), packfile_index_stored
     plakar_amd.archive     a snapshot's entries as one tar or tar.gz stream (ArchiveSession, archive_files);
                            a gzip member written piece by piece on the device (GzipStream)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "archive", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "stored", "archive", "build"]

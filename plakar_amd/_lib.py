@@ -129,6 +129,23 @@ class cdc_packfile_row(ctypes.Structure):
                 ("type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
 
 
+# CDC_PACKFILE_* of the header, without the prefix (a module name that starts with CDC_ is a status code)
+PACKFILE_PLAIN, PACKFILE_STORED, PACKFILE_ROWS = 0, 1, 2
+
+
+def packfile_form_code(form):
+    """The C form for "plain" / "stored" (the packfile forms a writer makes); ValueError otherwise."""
+    try:
+        return {"plain": PACKFILE_PLAIN, "stored": PACKFILE_STORED}[form]
+    except (KeyError, TypeError):
+        raise ValueError(f"unsupported packfile form {form!r} (\"plain\" or \"stored\")") from None
+
+
+class cdc_packfile_src(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_void_p), ("len", ctypes.c_uint64), ("path", ctypes.c_char_p),
+                ("form", ctypes.c_int), ("rows", ctypes.POINTER(cdc_packfile_row)), ("nrows", ctypes.c_uint64)]
+
+
 class cdc_codec(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_char_p)]
 
@@ -444,6 +461,13 @@ SIGNATURES = {
                                                   ctypes.c_void_p]),
     "cdc_packfile_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, _P(cdc_packfile_footer),
                                           _P(cdc_packfile_row), ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_packfile_index_stored": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                 ctypes.c_char_p, _P(cdc_packfile_footer), _P(cdc_packfile_row),
+                                                 ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_packer_stored_bound": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "cdc_packer_serialize_stored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                   _P(ctypes.c_uint64)]),
     "cdc_assemble_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
                                            _P(ctypes.c_uint64), _P(ctypes.c_uint64), ctypes.c_uint64,
                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
@@ -452,6 +476,8 @@ SIGNATURES = {
     "cdc_restore_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_restore_opts), _P(ctypes.c_void_p)]),
     "cdc_restore_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_restore_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_restore_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
     "cdc_restore_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, RESTORE_FILE_FN,
                                          ctypes.c_void_p, _P(cdc_restore_stats)]),
     "cdc_restore_ranges": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_restore_file), ctypes.c_int, _P(cdc_read_range),
@@ -464,6 +490,8 @@ SIGNATURES = {
     "cdc_check_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_check_opts), _P(ctypes.c_void_p)]),
     "cdc_check_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_check_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_check_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
     "cdc_check_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_check_file), ctypes.c_int, CHECK_FILE_FN,
                                        ctypes.c_void_p, _P(cdc_check_stats)]),
     "cdc_check_free": (None, [ctypes.c_void_p]),
@@ -488,6 +516,8 @@ SIGNATURES = {
     "cdc_diff_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_diff_opts), _P(ctypes.c_void_p)]),
     "cdc_diff_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_diff_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_diff_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
     "cdc_diff_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_diff_pair), ctypes.c_int, DIFF_PAIR_FN,
                                       ctypes.c_void_p, _P(cdc_diff_stats)]),
     "cdc_diff_free": (None, [ctypes.c_void_p]),
@@ -495,14 +525,19 @@ SIGNATURES = {
     "cdc_sync_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_sync_opts), _P(ctypes.c_void_p)]),
     "cdc_sync_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_sync_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_sync_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
     "cdc_sync_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, BACKUP_PACK_FN, SYNC_BLOB_FN,
                                     ctypes.c_void_p, _P(cdc_sync_stats)]),
     "cdc_sync_free": (None, [ctypes.c_void_p]),
+    "cdc_sync_set_packfile_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cdc_archive_default_opts": (None, [_P(cdc_archive_opts)]),
     "cdc_archive_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_new_zip": (ctypes.c_int, [ctypes.c_int, _P(cdc_archive_opts), _P(ctypes.c_void_p)]),
     "cdc_archive_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "cdc_archive_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_archive_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
     "cdc_archive_run": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_archive_entry), ctypes.c_int, ctypes.c_char_p,
                                        ARCHIVE_DATA_FN, ARCHIVE_ENTRY_FN, ctypes.c_void_p, _P(cdc_archive_stats)]),
     "cdc_archive_free": (None, [ctypes.c_void_p]),
@@ -520,6 +555,7 @@ SIGNATURES = {
                                         BACKUP_PACK_FN, ctypes.c_void_p, _P(cdc_backup_stats)]),
     "cdc_backup_free": (None, [ctypes.c_void_p]),
     "cdc_backup_set_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "cdc_backup_set_packfile_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cdc_sha256": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, _P(ctypes.c_uint8)]),
     "cdc_sha256_accelerated": (ctypes.c_int, []),
     "cdc_chunk_entropy_device_async": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,

@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import stored as _stored
 from ._lib import check, ensure_init, lib
 
 DEFAULT_BATCH_BYTES = 256 << 20
@@ -173,6 +174,18 @@ class ArchiveSession:
         check(lib().cdc_archive_add_packfile(self._h, buf, len(buf)), "cdc_archive_add_packfile")
         self._keep.append(buf)
 
+    def add_packfiles(self, packfiles, form="plain", rows=None):
+        """Register many packfiles (bytes and/or paths) in one call
+        (cdc_archive_add_packfiles): form "plain" or "stored", the form a repository
+        keeps, whose footers and indexes are all decoded in two device calls;
+        or rows, one list of (type, checksum, offset, length) per packfile
+        (the repository state's), and nothing of a file's tail is read.
+        Returns the per-source statuses: 0, or the CDC_E_* code of a source
+        that was not entered."""
+        if not self._h:
+            raise ValueError("session closed")
+        return _stored.add_packfiles("cdc_archive_add_packfiles", self._h, self._keep, packfiles, form, rows)
+
     def run(self, entries, path=None, on_data=None):
         """Write the entries (ArchiveEntry, in order) as one archive to `path`,
         or hand its bytes in order to on_data(bytes) (the reference's "-"), or
@@ -266,13 +279,12 @@ class ZipSession(ArchiveSession):
 
 
 def zip_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", verify=True, writers=8,
-              batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):
+              batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0, packfile_form="plain"):
     """One zip archive through the native pipeline (a ZipSession for this call
     only).  Returns (data, statuses, stats) as ArchiveSession.run; a
     directory's status is 0 though nothing is written for it."""
     with ZipSession(key, compression, verify, writers, batch_bytes, device, level) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(entries, path, on_data)
 
 
@@ -325,13 +337,12 @@ def zip_pieces_device(src, pieces, headers, out, out_cap=None, device=0, stream=
 
 
 def archive_files(entries, packfiles, path=None, on_data=None, key=None, compression="LZ4", format="tarball",
-                  verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0):
+                  verify=True, writers=8, batch_bytes=DEFAULT_BATCH_BYTES, device=0, level=0, packfile_form="plain"):
     """One archive through the native pipeline (an ArchiveSession for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (data, statuses, stats) as ArchiveSession.run."""
     with ArchiveSession(key, compression, format, verify, writers, batch_bytes, device, level) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(entries, path, on_data)
 
 

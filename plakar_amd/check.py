@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import stored as _stored
 from ._lib import check, ensure_init, lib
 
 DEFAULT_BATCH_BYTES = 256 << 20
@@ -89,6 +90,18 @@ class CheckSession:
         check(lib().cdc_check_add_packfile(self._h, buf, len(buf)), "cdc_check_add_packfile")
         self._keep.append(buf)
 
+    def add_packfiles(self, packfiles, form="plain", rows=None):
+        """Register many packfiles (bytes and/or paths) in one call
+        (cdc_check_add_packfiles): form "plain" or "stored", the form a repository
+        keeps, whose footers and indexes are all decoded in two device calls;
+        or rows, one list of (type, checksum, offset, length) per packfile
+        (the repository state's), and nothing of a file's tail is read.
+        Returns the per-source statuses: 0, or the CDC_E_* code of a source
+        that was not entered."""
+        if not self._h:
+            raise ValueError("session closed")
+        return _stored.add_packfiles("cdc_check_add_packfiles", self._h, self._keep, packfiles, form, rows)
+
     def run(self, objects, verify_checksum=True):
         """Check the objects (snapshot.Object: Chunks' Checksum and Length, and
         Checksum).  verify_checksum=False only computes the object checksums
@@ -161,13 +174,12 @@ class CheckSession:
 
 
 def check_files(objects, packfiles, key=None, compression="LZ4", fast=False, threads=8,
-                batch_bytes=DEFAULT_BATCH_BYTES, host_min_len=0, device=0, verify_checksum=True):
+                batch_bytes=DEFAULT_BATCH_BYTES, host_min_len=0, device=0, verify_checksum=True, packfile_form="plain"):
     """One check through the native pipeline (a CheckSession for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (results, stats) as CheckSession.run."""
     with CheckSession(key, compression, fast, threads, batch_bytes, host_min_len, device) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(objects, verify_checksum)
 
 

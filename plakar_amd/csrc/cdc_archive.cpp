@@ -51,6 +51,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "cdc_stored.h"
 #include "deflate_enc.h"
 #include "inflate_walk.h"
 #include "zip_plan.h"
@@ -92,6 +93,7 @@ struct cdc_archive {
     hipStream_t stream = nullptr;
     cdc::PinBuf h_in, h_out;
     cdc::DevBuf d_in, d_plain, d_img, d_gz;
+    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_archive_add_packfiles)
     std::mutex run_mu;
 };
 
@@ -630,6 +632,18 @@ int cdc_archive_add_packfile_path(cdc_archive *a, const char *path)
     std::lock_guard<std::mutex> lk(a->run_mu);
     try {
         return a->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_archive_add_packfiles(cdc_archive *a, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
+{
+    if (!a || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(a->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    try {
+        return cdc::add_packfiles(a->loc, a->stored, a->device, a->o.compress, a->key.empty() ? nullptr : a->key.data(), srcs, n, status);
     } catch (...) {
         return CDC_E_NOMEM;
     }

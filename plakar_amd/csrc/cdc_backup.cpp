@@ -54,6 +54,7 @@
 
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
+#include "cdc_stored.h"
 
 namespace {
 
@@ -242,6 +243,8 @@ struct cdc_backup {
     hipStream_t stream[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int hw_queues = 0;  // GPU_MAX_HW_QUEUES at cdc_backup_new (0: unset)
     std::atomic<int> level{CDC_LEVEL_FAST};  // cdc_backup_set_level: Encode's match search in later runs
+    std::atomic<int> pack_form{CDC_PACKFILE_PLAIN};  // cdc_backup_set_packfile_form: what on_pack receives in later runs
+    std::unique_ptr<cdc::StoredCodec> stored;        // the stored form's codec, made by the first run that needs it
 };
 
 namespace {
@@ -266,6 +269,8 @@ struct Run {
     cdc_backup *B;
     const cdc_backup_opts &o;
     const int level;  // the session's when the run began
+    cdc::StoredCodec *stored = nullptr;  // the stored form (the session's when the run began): used under sink_mu
+    std::vector<uint8_t> tail;           // its scratch (sink_mu)
     const char *const *paths;
     int n;
     cdc_backup_file_fn on_file;
@@ -622,6 +627,15 @@ int sink(Run &R, cdc_packer *p)
 {
     const uint8_t *data = nullptr;
     uint64_t len = 0;
+    if (R.stored) {  // PutPackfile's form: one codec for the run, under the lock that serialises on_pack
+        std::lock_guard<std::mutex> lk(R.sink_mu);
+        const int st = cdc::seal_stored(*R.stored, p, R.o.timestamp, R.tail, &data, &len);
+        if (st != CDC_OK) return st;
+        R.ev("packfile", -1, -1, len);
+        ++R.st.packfiles;
+        R.st.packed_bytes += len;
+        return R.on_pack ? R.on_pack(R.ctx, data, len) : CDC_OK;
+    }
     const int st = cdc::packer_seal(p, R.o.timestamp, &data, &len);
     if (st != CDC_OK) return st;
     R.ev("packfile", -1, -1, len);
@@ -1197,6 +1211,13 @@ int cdc_backup_set_level(cdc_backup *B, int level)
     return CDC_OK;
 }
 
+int cdc_backup_set_packfile_form(cdc_backup *B, int form)
+{
+    if (!B || (form != CDC_PACKFILE_PLAIN && form != CDC_PACKFILE_STORED)) return CDC_E_INVALID;
+    B->pack_form.store(form);
+    return CDC_OK;
+}
+
 int cdc_backup_files(cdc_backup *B, const char *const *paths, int n, cdc_backup_file_fn on_file,
                      cdc_backup_pack_fn on_pack, void *ctx, cdc_backup_stats *stats)
 {
@@ -1223,6 +1244,14 @@ int cdc_backup_files(cdc_backup *B, const char *const *paths, int n, cdc_backup_
         R.st.slot_arena_bytes = arena;
         R.ev("planned", -1, -1, uint64_t(R.batches.size()));
         if (st == CDC_OK && hipSetDevice(B->device) != hipSuccess) st = CDC_E_DEVICE;
+        if (st == CDC_OK && B->pack_form.load() == CDC_PACKFILE_STORED) {
+            if (!B->stored) {
+                std::unique_ptr<cdc::StoredCodec> c(new cdc::StoredCodec());
+                st = c->open(B->device, R.o.compress, R.o.key);
+                if (st == CDC_OK) B->stored = std::move(c);
+            }
+            R.stored = B->stored.get();
+        }
         if (st == CDC_OK && R.trace_path) {
             if (hipEventCreate(&R.trace_ref) != hipSuccess || hipEventRecord(R.trace_ref, B->stream[kA]) != hipSuccess ||
                 hipEventSynchronize(R.trace_ref) != hipSuccess)

@@ -41,6 +41,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "cdc_stored.h"
 #include "check_plan.h"
 #include "restore_plan.h"
 
@@ -168,6 +169,7 @@ struct cdc_check {
     OutSlot out[2];
     cdc::DevBuf plain, dig;
     cdc::PinBuf hdig;
+    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_check_add_packfiles)
     std::mutex run_mu;
 };
 
@@ -659,6 +661,18 @@ int cdc_check_add_packfile_path(cdc_check *c, const char *path)
     std::lock_guard<std::mutex> lk(c->run_mu);
     try {
         return c->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_check_add_packfiles(cdc_check *c, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
+{
+    if (!c || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(c->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    try {
+        return cdc::add_packfiles(c->loc, c->stored, c->device, c->o.compress, c->key.empty() ? nullptr : c->key.data(), srcs, n, status);
     } catch (...) {
         return CDC_E_NOMEM;
     }

@@ -38,6 +38,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "cdc_stored.h"
 #include "diff_plan.h"
 #include "restore_plan.h"
 
@@ -77,6 +78,7 @@ struct cdc_diff {
     hipStream_t stream = nullptr;
     cdc::PinBuf hin, hrecs, hlit, hout;
     cdc::DevBuf din, plain, image, recs, lit, out;
+    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_diff_add_packfiles)
     std::mutex run_mu;
 };
 
@@ -587,6 +589,18 @@ int cdc_diff_add_packfile_path(cdc_diff *d, const char *path)
     std::lock_guard<std::mutex> lk(d->run_mu);
     try {
         return d->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_diff_add_packfiles(cdc_diff *d, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
+{
+    if (!d || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(d->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    try {
+        return cdc::add_packfiles(d->loc, d->stored, d->device, d->o.compress, d->key.empty() ? nullptr : d->key.data(), srcs, n, status);
     } catch (...) {
         return CDC_E_NOMEM;
     }

@@ -263,6 +263,10 @@ inline bool level_ok(int level) { return level == CDC_LEVEL_FAST || level == CDC
 // cdc_packer.cpp: in-place serialization for the backup pipeline's sinks
 int packer_seal(cdc_packer *p, int64_t timestamp, const uint8_t **data, uint64_t *len);
 void packer_reserve(cdc_packer *p, uint64_t max_blob);
+// the stored form's sink (cdc_stored.cpp): the parts to Encode, and the encoded tail appended
+void packer_tail_parts(const cdc_packer *p, int64_t timestamp, const uint8_t **index, uint64_t *index_len,
+                       uint8_t footer[52]);
+int packer_seal_tail(cdc_packer *p, const uint8_t *tail, uint64_t n, const uint8_t **data, uint64_t *len);
 
 }  // namespace cdc
 

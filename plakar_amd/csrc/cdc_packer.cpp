@@ -165,6 +165,29 @@ int packer_seal(cdc_packer *p, int64_t timestamp, const uint8_t **data, uint64_t
     return CDC_OK;
 }
 
+// The stored form's sink (PutPackfile, snapshot/snapshot.go:249-267): the index
+// and the footer as Serialize writes them, for the caller to Encode ...
+void packer_tail_parts(const cdc_packer *p, int64_t timestamp, const uint8_t **index, uint64_t *index_len,
+                       uint8_t footer[52])
+{
+    std::vector<uint8_t> f;
+    serialize_footer(p, timestamp, f);
+    std::memcpy(footer, f.data(), kFooterBytes);
+    *index = p->index.data();
+    *index_len = p->index.size();
+}
+
+// ... and what it made of them appended to the data section, as packer_seal
+// appends the plain ones.
+int packer_seal_tail(cdc_packer *p, const uint8_t *tail, uint64_t n, const uint8_t **data, uint64_t *len)
+{
+    if (!p || !data || !len || (n && !tail)) return CDC_E_INVALID;
+    p->blobs.insert(p->blobs.end(), tail, tail + n);
+    *data = p->blobs.data();
+    *len = p->blobs.size();
+    return CDC_OK;
+}
+
 void packer_reserve(cdc_packer *p, uint64_t max_blob)
 {
     if (!p) return;

@@ -42,6 +42,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "cdc_stored.h"
 #include "read_plan.h"
 #include "restore_plan.h"
 
@@ -105,6 +106,7 @@ struct cdc_restore {
     InSlot in[2];
     OutSlot out[2];
     cdc::DevBuf plain;
+    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_restore_add_packfiles)
     std::mutex run_mu;
 };
 
@@ -752,6 +754,18 @@ int cdc_restore_add_packfile_path(cdc_restore *r, const char *path)
     std::lock_guard<std::mutex> lk(r->run_mu);
     try {
         return r->loc.add_path(path);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
+int cdc_restore_add_packfiles(cdc_restore *r, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
+{
+    if (!r || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(r->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    try {
+        return cdc::add_packfiles(r->loc, r->stored, r->device, r->o.compress, r->key.empty() ? nullptr : r->key.data(), srcs, n, status);
     } catch (...) {
         return CDC_E_NOMEM;
     }

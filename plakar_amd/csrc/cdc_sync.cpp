@@ -43,6 +43,7 @@
 #include "cdc_hostmem.h"
 #include "cdc_internal.h"
 #include "cdc_locator.h"
+#include "cdc_stored.h"
 #include "sync_plan.h"
 #include "transcode_plan.h"
 
@@ -108,6 +109,9 @@ struct cdc_sync {
     InSlot in[2];
     OutSlot out[2];
     std::vector<cdc_packer *> packers;
+    int dst_form = CDC_PACKFILE_PLAIN;              // cdc_sync_set_packfile_form
+    std::unique_ptr<cdc::StoredCodec> dst_stored;   // the destination's stored-form codec, made by the first run that needs it
+    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_sync_add_packfiles)
     std::mutex run_mu;
 };
 
@@ -126,6 +130,8 @@ struct Run {
     int fail = CDC_OK;
     std::mutex sink_mu;  // on_pack is serialised; `stopped`: it returned a negative status
     bool stopped = false;
+    cdc::StoredCodec *stored = nullptr;  // the destination's stored form: one codec for the run, used under sink_mu
+    std::vector<uint8_t> tail;           // its scratch (sink_mu)
     cdc_sync_stats st{};
 
     const cdc_packfile_row &row(const splan::Item &it) const { return S->loc.rows[it.pack][it.row]; }
@@ -308,9 +314,13 @@ static void sink(Run &X, cdc_packer *p)
 {
     const uint8_t *data = nullptr;
     uint64_t len = 0;
-    int st = cdc::packer_seal(p, X.S->o.timestamp, &data, &len);
+    int st = X.stored ? CDC_OK : cdc::packer_seal(p, X.S->o.timestamp, &data, &len);
     if (st == CDC_OK) {
         std::lock_guard<std::mutex> lk(X.sink_mu);
+        if (!X.stopped && X.stored) {  // PutPackfile's form: the index and the footer through Encode
+            st = cdc::seal_stored(*X.stored, p, X.S->o.timestamp, X.tail, &data, &len);
+            if (st != CDC_OK) X.stopped = true;
+        }
         if (!X.stopped) {
             ++X.st.packfiles;
             X.st.packed_bytes += len;
@@ -395,6 +405,15 @@ static int run_sync(cdc_sync *S, const uint8_t *wanted, uint64_t nwanted, cdc_ba
     for (cdc_packer *pk : S->packers) cdc_packer_reset(pk);
     if (!X.plan.batches.empty()) {
         if (hipSetDevice(S->device) != hipSuccess) return CDC_E_DEVICE;
+        if (S->dst_form == CDC_PACKFILE_STORED) {
+            if (!S->dst_stored) {
+                std::unique_ptr<cdc::StoredCodec> c(new cdc::StoredCodec());
+                const int st = c->open(S->device, S->dst.compress, S->dst.key);
+                if (st != CDC_OK) return st;
+                S->dst_stored = std::move(c);
+            }
+            X.stored = S->dst_stored.get();
+        }
         auto guarded = [&X](void (*stage)(Run &)) {
             try {
                 stage(X);
@@ -495,6 +514,18 @@ int cdc_sync_add_packfile_path(cdc_sync *s, const char *path)
     }
 }
 
+int cdc_sync_add_packfiles(cdc_sync *s, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
+{
+    if (!s || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(s->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    try {
+        return cdc::add_packfiles(s->loc, s->stored, s->device, s->src.compress, s->src.key, srcs, n, status);
+    } catch (...) {
+        return CDC_E_NOMEM;
+    }
+}
+
 int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack, cdc_sync_blob_fn on_fail,
                  void *ctx, cdc_sync_stats *stats)
 {
@@ -506,6 +537,15 @@ int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backu
     } catch (const std::bad_alloc &) {
         return CDC_E_NOMEM;
     }
+}
+
+int cdc_sync_set_packfile_form(cdc_sync *s, int form)
+{
+    if (!s || (form != CDC_PACKFILE_PLAIN && form != CDC_PACKFILE_STORED)) return CDC_E_INVALID;
+    std::unique_lock<std::mutex> lk(s->run_mu, std::try_to_lock);
+    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
+    s->dst_form = form;
+    return CDC_OK;
 }
 
 void cdc_sync_free(cdc_sync *s)

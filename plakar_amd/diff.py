@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import stored as _stored
 from ._lib import check, ensure_init, lib
 
 DEFAULT_BATCH_BYTES = 256 << 20
@@ -230,6 +231,18 @@ class DiffSession:
         check(lib().cdc_diff_add_packfile(self._h, buf, len(buf)), "cdc_diff_add_packfile")
         self._keep.append(buf)
 
+    def add_packfiles(self, packfiles, form="plain", rows=None):
+        """Register many packfiles (bytes and/or paths) in one call
+        (cdc_diff_add_packfiles): form "plain" or "stored", the form a repository
+        keeps, whose footers and indexes are all decoded in two device calls;
+        or rows, one list of (type, checksum, offset, length) per packfile
+        (the repository state's), and nothing of a file's tail is read.
+        Returns the per-source statuses: 0, or the CDC_E_* code of a source
+        that was not entered."""
+        if not self._h:
+            raise ValueError("session closed")
+        return _stored.add_packfiles("cdc_diff_add_packfiles", self._h, self._keep, packfiles, form, rows)
+
     def run(self, pairs):
         """Diff the pairs, each (object_a, object_b, from_name, to_name) with
         snapshot.Objects (Chunks' Checksum and Length, and Checksum or None).
@@ -291,13 +304,12 @@ class DiffSession:
 
 
 def diff_files(pairs, packfiles, key=None, compression="LZ4", context=3, threads=8, batch_bytes=DEFAULT_BATCH_BYTES,
-               max_lines=0, hash_bits=0, device=0):
+               max_lines=0, hash_bits=0, device=0, packfile_form="plain"):
     """One diff through the native pipeline (a DiffSession for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (results, stats) as DiffSession.run."""
     with DiffSession(key, compression, context, threads, batch_bytes, max_lines, hash_bits, device) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(pairs)
 
 

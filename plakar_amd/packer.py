@@ -71,9 +71,24 @@ class Packer:
         """0 SerializeData, 1 SerializeIndex, 2 SerializeFooter."""
         return self._bytes(lib().cdc_packer_serialize_part, int(part), ctypes.c_int64(self.timestamp))
 
-    def PutPackfileBytes(self, encode=lambda b: b):
+    def PutPackfileBytes(self, encode=lambda b: b, device=None, key=None, compression="LZ4", random=None):
         """The bytes PutPackfile stores (snapshot/snapshot.go:236-267): data, Encode(index),
-        Encode(footer), version u32 little-endian, u8 length of Encode(footer)."""
+        Encode(footer), version u32 little-endian, u8 length of Encode(footer).  With device=
+        the index and the footer go through Encode on that device (cdc_packer_serialize_stored;
+        key: 32 bytes or None, compression "LZ4", "GZIP" or None, random: 112 bytes, the index's
+        56 then the footer's, or None: drawn by the library); otherwise through `encode`."""
+        if device is not None:
+            code = _lib.compress_code(compression)
+            if key is not None:
+                key = bytes(key)
+                if len(key) != 32:
+                    raise ValueError("the repository key is 32 bytes (AES-256)")
+            if random is not None:
+                random = bytes(random)
+                if len(random) != 112:
+                    raise ValueError("random: 112 bytes (56 for the index, 56 for the footer)")
+            return self._bytes(lib().cdc_packer_serialize_stored, ctypes.c_int64(self.timestamp), int(device), code, key,
+                               random)
         data, idx, foot = self.SerializePart(0), self.SerializePart(1), self.SerializePart(2)
         ef = encode(foot)
         return data + encode(idx) + ef + struct.pack("<I", 100) + bytes([len(ef) & 0xFF])

@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import stored as _stored
 from ._lib import check, ensure_init, lib
 
 DEFAULT_BATCH_BYTES = 256 << 20
@@ -40,6 +41,9 @@ def packfile_index(data):
     footer = dict(version=int(f.version), timestamp=int(f.timestamp), count=int(f.count),
                   index_offset=int(f.index_offset), index_checksum=bytes(f.index_checksum))
     return footer, [(int(r.type), bytes(r.checksum), int(r.offset), int(r.length)) for r in (rows or [])]
+
+
+packfile_index_stored = _stored.packfile_index_stored
 
 
 def _u64(a):
@@ -121,6 +125,18 @@ class RestoreSession:
         buf = bytes(packfile)
         check(lib().cdc_restore_add_packfile(self._h, buf, len(buf)), "cdc_restore_add_packfile")
         self._keep.append(buf)
+
+    def add_packfiles(self, packfiles, form="plain", rows=None):
+        """Register many packfiles (bytes and/or paths) in one call
+        (cdc_restore_add_packfiles): form "plain" or "stored", the form a repository
+        keeps, whose footers and indexes are all decoded in two device calls;
+        or rows, one list of (type, checksum, offset, length) per packfile
+        (the repository state's), and nothing of a file's tail is read.
+        Returns the per-source statuses: 0, or the CDC_E_* code of a source
+        that was not entered."""
+        if not self._h:
+            raise ValueError("session closed")
+        return _stored.add_packfiles("cdc_restore_add_packfiles", self._h, self._keep, packfiles, form, rows)
 
     def run(self, objects, dests=None):
         """Restore the objects (snapshot.Object, as backup_files returns them;
@@ -222,23 +238,21 @@ class RestoreSession:
 
 
 def restore_files(objects, packfiles, dests=None, key=None, compression="LZ4", verify=True, writers=8,
-                  batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+                  batch_bytes=DEFAULT_BATCH_BYTES, device=0, packfile_form="plain"):
     """One restore through the native pipeline (a RestoreSession for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (contents, statuses, stats) as RestoreSession.run."""
     with RestoreSession(key, compression, verify, writers, batch_bytes, device) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(objects, dests)
 
 
 def read_ranges(objects, ranges, packfiles, key=None, compression="LZ4", verify=True, writers=8,
-                batch_bytes=DEFAULT_BATCH_BYTES, device=0):
+                batch_bytes=DEFAULT_BATCH_BYTES, device=0, packfile_form="plain"):
     """One ranged read through the native pipeline (a RestoreSession for this
     call only), as restore_files.  Returns what RestoreSession.read_ranges does."""
     with RestoreSession(key, compression, verify, writers, batch_bytes, device) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+        _stored.add_all(s, packfiles, packfile_form)
         return s.read_ranges(objects, ranges)
 
 
@@ -331,5 +345,5 @@ class SnapshotFile(io.RawIOBase):
         return len(data)
 
 
-__all__ = ["packfile_index", "assemble_device", "RestoreSession", "restore_files", "read_ranges", "SnapshotFile",
+__all__ = ["packfile_index", "packfile_index_stored", "assemble_device", "RestoreSession", "restore_files", "read_ranges", "SnapshotFile",
            "DEFAULT_BATCH_BYTES"]

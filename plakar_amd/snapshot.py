@@ -305,18 +305,23 @@ class BackupSession:
     histograms, dedup, Encode, `packers` concurrent packerJob workers,
     snapshot/snapshot.go:51-92).  `level`: Encode's match search in this
     session's runs (0; 1: a 32-KiB window, smaller blobs; 9: four candidates per
-    bucket and a lazy parse, the smallest; cdc_backup_set_level)."""
+    bucket and a lazy parse, the smallest; cdc_backup_set_level).
+    `packfile_form`: "plain" (Serialize's form) or "stored", the bytes
+    repository.PutPackfile stores (cdc_backup_set_packfile_form)."""
 
     def __init__(self, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
-                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, level=0):
+                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, level=0, packfile_form="plain"):
         import ctypes
         from . import _lib
         level = _lib.level_code(level)  # ValueError for any value but 0, 1 and 9
+        form = _lib.packfile_form_code(packfile_form)  # ValueError for any name but "plain" and "stored"
         o = self._opts(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp)
         self._h = ctypes.c_void_p()
         _lib.check(_lib.lib().cdc_backup_new(int(dev), ctypes.byref(o), ctypes.byref(self._h)), "cdc_backup_new")
         if level:
             _lib.check(_lib.lib().cdc_backup_set_level(self._h, level), "cdc_backup_set_level")
+        if form:
+            _lib.check(_lib.lib().cdc_backup_set_packfile_form(self._h, form), "cdc_backup_set_packfile_form")
 
     def _opts(self, repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp):
         """The cdc_backup_opts of these arguments; the buffers it points to stay with self."""
@@ -470,15 +475,21 @@ class _BackupRun(BackupSession):
 
 
 def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", known=None, max_size=None,
-                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, keep_packfiles=True, level=0):
+                 packers=8, readers=8, batch_bytes=256 << 20, timestamp=0, dev=0, keep_packfiles=True, level=0,
+                 packfile_form="plain"):
     """One backup of a list of files through the native pipeline
-    (cdc_backup_run_level: a context for this call only; `level` as
-    BackupSession's).  known: iterable of 32-byte digests
+    (cdc_backup_run_level: a context for this call only; `level` and
+    `packfile_form` as BackupSession's, and a form other than "plain" goes
+    through a BackupSession for this call).  known: iterable of 32-byte digests
     already in the repository (not stored again).  Returns (objects,
     packfiles, stats): one Object per path in order (entropy and
     Distribution computed here from the device histograms, as chunkify_batch
     does), the serialised packfiles in the order the packers flushed them,
     and the per-stage stats of cdc_backup_stats."""
+    if packfile_form != "plain":
+        with BackupSession(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp, dev, level,
+                           packfile_form) as s:
+            return s.run(paths, keep_packfiles)
     with _BackupRun(repo, key, compression, known, max_size, packers, readers, batch_bytes, timestamp, dev, level) as s:
         return s.run(paths, keep_packfiles)
 

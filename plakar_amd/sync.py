@@ -15,8 +15,11 @@ blobs are never copied in Python.  Every device call goes through the C ABI
 (cdc_transcode_device, cdc_transcode_size, cdc_sync_*; cdc_packfile_index and
 cdc_packer_* through restore.packfile_index and packer.Packer).
 
-Out of scope: the PutPackfile stored form of a packfile (restore does not read
-it either), the snapshot, state and header records, and more than one device."""
+SyncPipeline reads and writes packfiles in either form: the plain Serialize
+form, or the form a repository keeps (PutPackfile; stored.py), per source with
+add_packfiles(form=) and for the destination with dst_packfile_form=.
+
+Out of scope: the snapshot, state and header records, and more than one device."""
 import ctypes
 import os
 import time
@@ -24,6 +27,7 @@ import time
 import numpy as np
 
 from . import _lib, packer
+from . import stored as _stored
 from ._lib import CdcError, ensure_init, lib
 from .decode import _key, _ptr, _u64, _upload
 from .encode import RANDOM_BYTES, _reservoir, encode_bound
@@ -288,9 +292,10 @@ class SyncPipeline:
 
     def __init__(self, src_key=None, src_compression="LZ4", dst_key=None, dst_compression="LZ4", verify=True,
                  known=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0, level=0,
-                 readers=0, packers=0):
+                 readers=0, packers=0, dst_packfile_form="plain"):
         self._h = None
         self._keep = []  # packfile bytes the context reads from until it is freed
+        dst_form = _lib.packfile_form_code(dst_packfile_form)
         level = _lib.level_code(level)
         self.src, self.dst = (src_key, src_compression), (dst_key, dst_compression)
         (skey, scomp), (dkey, dcomp) = _codec(self.src), _codec(self.dst)  # ValueError for a bad key or name
@@ -310,6 +315,8 @@ class SyncPipeline:
         h = ctypes.c_void_p()
         _lib.check(lib().cdc_sync_new(int(device), ctypes.byref(o), ctypes.byref(h)), "cdc_sync_new")
         self._h = h
+        if dst_form != _lib.PACKFILE_PLAIN:
+            _lib.check(lib().cdc_sync_set_packfile_form(self._h, dst_form), "cdc_sync_set_packfile_form")
 
     def add_packfile(self, packfile):
         """Register a source packfile: bytes (kept alive by the context) or a
@@ -323,6 +330,18 @@ class SyncPipeline:
         buf = bytes(packfile)
         _lib.check(lib().cdc_sync_add_packfile(self._h, buf, len(buf)), "cdc_sync_add_packfile")
         self._keep.append(buf)
+
+    def add_packfiles(self, packfiles, form="plain", rows=None):
+        """Register many source packfiles (bytes and/or paths) in one call
+        (cdc_sync_add_packfiles): form "plain" or "stored", the form a
+        repository keeps, whose footers and indexes are all decoded with the
+        source codec in two device calls; or rows, one list of (type,
+        checksum, offset, length) per packfile (the repository state's), and
+        nothing of a file's tail is read.  Returns the per-source statuses: 0,
+        or the CDC_E_* code of a source that was not entered."""
+        if not self._h:
+            raise ValueError("pipeline closed")
+        return _stored.add_packfiles("cdc_sync_add_packfiles", self._h, self._keep, packfiles, form, rows)
 
     def run(self, wanted=None, on_pack=None):
         """One sync (cdc_sync_run).  Returns (packfiles, failures, stats) as
@@ -387,14 +406,13 @@ class SyncPipeline:
 
 def sync_packfiles(packfiles, src_key=None, src_compression="LZ4", dst_key=None, dst_compression="LZ4", verify=True,
                    known=None, wanted=None, max_size=None, batch_bytes=DEFAULT_BATCH_BYTES, timestamp=None, device=0,
-                   level=0, readers=0, packers=0):
+                   level=0, readers=0, packers=0, packfile_form="plain", dst_packfile_form="plain"):
     """One sync through the native pipeline (a SyncPipeline for this call
     only): packfiles is a list of serialised packfiles (bytes) and/or paths.
     Returns (packfiles, failures, stats) as SyncPipeline.run."""
     with SyncPipeline(src_key, src_compression, dst_key, dst_compression, verify, known, max_size, batch_bytes,
-                      timestamp, device, level, readers, packers) as s:
-        for p in packfiles:
-            s.add_packfile(p)
+                      timestamp, device, level, readers, packers, dst_packfile_form) as s:
+        _stored.add_all(s, packfiles, packfile_form)
         return s.run(wanted)
 
 

@@ -11,7 +11,20 @@ path the reference takes: tests/crypto_ref.decode per chunk occurrence on
 1 GiB of 64-KiB..4-MiB segments at odd source and destination alignments with
 hipEvents, under each cache policy, against a same-device tensor copy (torch
 issues it as hipMemcpyAsync device-to-device) of the same bytes in the same
-process."""
+process.
+
+    python tools/restore_bench.py --stored [--size-mib 1024] [--reps 3] [--out profiles/stored_form.json]
+
+measures what registering packfiles costs in the form a repository keeps
+(snapshot.PutPackfile) beside the plain form: one chunk set (--size-mib of C1
+bytes in 16-KiB chunks, 65,536 of them at 1 GiB, under a key and LZ4) is laid
+out once as packfiles of 64 rows (1,024 at 1 GiB) and once as packfiles of the
+default MaxSize, each written to disk in both forms.  Per layout, in one
+process and alternated, --reps times after a warm-up: add_packfile(path) per
+plain packfile (the yardstick), one add_packfiles(form="stored") call, and one
+add_packfiles call per stored packfile; then a restore of every file from a
+session of each kind.  One JSON line per layout with every repetition's
+seconds, medians and spreads ((max - min) / median)."""
 import argparse
 import json
 import os
@@ -77,6 +90,112 @@ def bench_assemble(a, torch, np):
     print(json.dumps(line), flush=True)
 
 
+def bench_stored(a):
+    import hashlib
+    import statistics
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    from plakar_amd import _lib, encode, packer, restore
+    _lib.ensure_init()
+    dev = torch.device("cuda", 0)
+    key = os.urandom(32)
+    chunk, per_file = 16 << 10, 1024
+    size = (a.size_mib << 20) // (chunk * per_file) * (chunk * per_file)
+    buf = bench.make_buffers(torch, bench.WORKLOADS["c1"], 0, dev, size)[0]
+    n = size // chunk
+    offs, lens = np.arange(n, dtype=np.int64) * chunk, np.full(n, chunk, dtype=np.int64)
+    enc = torch.empty(encode.encode_bound(chunk, True, True) * n, dtype=torch.uint8, device=dev)
+    oo = encode.encode_device(buf, offs, lens, enc, key=key, compress=True)
+    blobs = enc[:int(oo[-1])].cpu().numpy()
+    plain = buf.cpu().numpy()
+    del enc, buf
+    sums = [hashlib.sha256(plain[i * chunk:(i + 1) * chunk]).digest() for i in range(n)]
+    objs = [types.SimpleNamespace(Chunks=[types.SimpleNamespace(Checksum=sums[i], Length=chunk)
+                                          for i in range(f * per_file, (f + 1) * per_file)]) for f in range(n // per_file)]
+    work = tempfile.mkdtemp(prefix="stored_bench_", dir=a.tmp)
+    records = []
+    try:
+        for layout, rows_per in (("64-row packfiles", 64), ("default packfiles", None)):
+            pk = packer.Packer(timestamp=1)
+            paths = {"plain": [], "stored": []}
+
+            def flush():
+                k = len(paths["plain"])
+                for form, data in (("plain", pk.Serialize()),
+                                   ("stored", pk.PutPackfileBytes(device=0, key=key, compression="LZ4"))):
+                    path = os.path.join(work, f"{rows_per}_{form}_{k:05d}")
+                    with open(path, "wb") as f:
+                        f.write(data)
+                    paths[form].append(path)
+                pk.Reset()
+
+            for i in range(n):
+                full = pk.AddBlob(1, sums[i], blobs[int(oo[i]):int(oo[i + 1])])
+                if (pk.Count() == rows_per) if rows_per else full:
+                    flush()
+            if pk.Count():
+                flush()
+            pk.close()
+            npacks = len(paths["plain"])
+
+            def register(kind):
+                s = restore.RestoreSession(key=key)
+                t0 = time.perf_counter()
+                if kind == "plain":
+                    for path in paths["plain"]:
+                        s.add_packfile(path)
+                elif kind == "stored_one_call":
+                    assert not any(s.add_packfiles(paths["stored"], form="stored"))
+                else:
+                    for path in paths["stored"]:
+                        assert s.add_packfiles([path], form="stored") == [0]
+                return s, time.perf_counter() - t0
+
+            kinds = ("plain", "stored_one_call", "stored_call_each")
+            for kind in kinds:  # warm: the codec's buffers, Decode's workspace, the page cache
+                register(kind)[0].close()
+            reg = {k: [] for k in kinds}
+            rst = {k: [] for k in kinds}
+            dests = [os.path.join(work, f"out{i:05d}") for i in range(len(objs))]
+            ok = True
+            for r in range(a.reps + 1):  # alternated; the first round grows the restore buffers and is dropped
+                for kind in kinds:
+                    s, t = register(kind)
+                    _, statuses, st = s.run(objs, dests)
+                    s.close()
+                    ok = ok and not any(statuses)
+                    if r:
+                        reg[kind].append(t)
+                        rst[kind].append(st["wall_s"])
+            k = len(dests) // 2
+            ok = ok and open(dests[k], "rb").read() == plain[k * per_file * chunk:(k + 1) * per_file * chunk].tobytes()
+            med = lambda v: statistics.median(v)  # noqa: E731
+            spread = lambda v: (max(v) - min(v)) / med(v)  # noqa: E731
+            rec = dict(layout=layout, packfiles=npacks, rows=n, rows_per_packfile=rows_per or n / npacks, bytes=size,
+                       reps=a.reps, round_trip_ok=bool(ok),
+                       stored_bytes=sum(os.path.getsize(x) for x in paths["stored"]),
+                       plain_bytes=sum(os.path.getsize(x) for x in paths["plain"]))
+            for kind in kinds:
+                rec[kind] = dict(register_s=reg[kind], register_median_s=med(reg[kind]), register_spread=spread(reg[kind]),
+                                 register_us_per_packfile=med(reg[kind]) / npacks * 1e6,
+                                 restore_wall_s=rst[kind], restore_median_s=med(rst[kind]), restore_spread=spread(rst[kind]))
+            rec["one_call_over_plain"] = rec["stored_one_call"]["register_median_s"] / rec["plain"]["register_median_s"]
+            rec["call_each_over_one_call"] = rec["stored_call_each"]["register_median_s"] / \
+                rec["stored_one_call"]["register_median_s"]
+            records.append(rec)
+            print(json.dumps(rec), flush=True)
+            for form in paths:
+                for path in paths[form]:
+                    os.remove(path)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="c1,c3,dup,assemble")
@@ -86,7 +205,17 @@ def main():
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--tmp", default=None, help="directory for the files (default: a temporary one)")
+    ap.add_argument("--stored", action="store_true", help="registration and restore: the stored form beside the plain")
+    ap.add_argument("--out", default=None, help="--stored: also write the records to this JSON file")
     a = ap.parse_args()
+    if a.stored:
+        records = bench_stored(a)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(dict(tool="tools/restore_bench.py --stored", records=records), f, indent=1)
+                f.write("\n")
+        return
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
 

@@ -23,6 +23,14 @@ and the same batch size.  One JSON line per set and leg, and all of them in
 profiles/sync_bench_pipeline.json: both walls with medians and spreads, the
 native run's stage seconds, the overlap it achieved (the sum of the stage
 walls over wall_s) and device_wait_s.
+
+    python tools/sync_bench.py --pipeline --stored [--out profiles/...json]
+
+times the native pipeline alone, in the form a repository keeps
+(snapshot.PutPackfile: stored packfiles in, stored packfiles out) beside the
+plain form (plain in, plain out), alternated in one process on the same blobs:
+what the destination's tail Encode per packfile adds to the wall, beside the
+spread of either.  The packers' busy time (pack_s) includes the tail's Encode.
 """
 import argparse
 import json
@@ -43,6 +51,45 @@ SETTINGS = {"rekey-lz4": ("LZ4", "LZ4"), "rekey-gzip": ("GZIP", "GZIP"), "lz4-to
 LEGS = {"rekey-verify": ("LZ4", True), "rekey": ("LZ4", False), "lz4-to-gzip": ("GZIP", True)}
 STAGES = ("read_s", "h2d_s", "transcode_s", "d2h_s", "pack_s", "callback_s")
 SESSION_STAGES = ("gather_s", "h2d_s", "transcode_s", "d2h_s", "pack_s")
+
+
+def stored_leg(a, name, leg, kw, packs, stored_packs, nblobs, torch, sync):
+    """One leg of --pipeline --stored: plain -> plain beside stored -> stored, alternated."""
+    import time
+    runs = {"plain": sync.SyncPipeline(packers=a.packers, **kw),
+            "stored": sync.SyncPipeline(packers=a.packers, dst_packfile_form="stored", **kw)}
+    for p in packs:
+        runs["plain"].add_packfile(p)
+    t0 = time.perf_counter()
+    assert not any(runs["stored"].add_packfiles(stored_packs, form="stored"))
+    register_s = time.perf_counter() - t0
+    for r in runs.values():
+        r.run()  # warm: workspace growth, tables, the slots' buffers, the codec's
+    walls, stats = {k: [] for k in runs}, {k: [] for k in runs}
+    out = {}
+    for _ in range(a.reps):
+        for k, r in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out[k], fail, st = r.run()
+            walls[k].append(time.perf_counter() - t0)
+            stats[k].append(st)
+            assert not fail
+    for r in runs.values():
+        r.close()
+    med = {k: statistics.median(v) for k, v in walls.items()}
+    spread = {k: (max(v) - min(v)) / med[k] for k, v in walls.items()}
+    stage = {k: {s: statistics.mean(st[s] for st in stats[k]) for s in STAGES + ("device_wait_s", "wall_s")} for k in runs}
+    added = med["stored"] - med["plain"]
+    noise = max(spread["plain"] * med["plain"], spread["stored"] * med["stored"])
+    return dict(set=name, leg=leg, blobs=nblobs, source_packfiles=len(packs), packfiles=len(out["stored"]),
+                packers=a.packers, size_mib=a.size_mib, reps=a.reps, batch_bytes=kw["batch_bytes"],
+                stored_register_s=register_s, plain_wall_s=walls["plain"], stored_wall_s=walls["stored"],
+                plain_median_s=med["plain"], stored_median_s=med["stored"], plain_spread=spread["plain"],
+                stored_spread=spread["stored"], stored_minus_plain_s=added, larger_spread_s=noise,
+                within_spread=bool(added <= noise), stage_s=stage,
+                stage_with_largest_increase=max(STAGES, key=lambda s: stage["stored"][s] - stage["plain"][s]),
+                plain_out_bytes=sum(len(p) for p in out["plain"]), stored_out_bytes=sum(len(p) for p in out["stored"]))
 
 
 def pipeline(a):
@@ -81,18 +128,24 @@ def pipeline(a):
         stored = enc[:int(oo[-1])].cpu().numpy()
         plain = buf.cpu().numpy()
         del enc, buf
-        packs, seen = [], set()
+        packs, stored_packs, seen = [], [], set()
         pk = packer.Packer(timestamp=1)
+
+        def flush():
+            packs.append(pk.Serialize())
+            if a.stored:
+                stored_packs.append(pk.PutPackfileBytes(device=0, key=key_a, compression="LZ4"))
+            pk.Reset()
+
         for i in range(len(lens)):
             digest = hashlib.sha256(plain[int(offs[i]):int(offs[i]) + int(lens[i])]).digest()
             if digest in seen:
                 continue
             seen.add(digest)
             if pk.AddBlob(1, digest, stored[int(oo[i]):int(oo[i + 1])]):
-                packs.append(pk.Serialize())
-                pk.Reset()
+                flush()
         if pk.Count():
-            packs.append(pk.Serialize())
+            flush()
         pk.close()
         nblobs, sbytes, pbytes = len(seen), sum(len(p) for p in packs), int(lens.sum())
         del stored, plain
@@ -100,6 +153,10 @@ def pipeline(a):
             dc, verify = LEGS[leg]
             kw = dict(src_key=key_a, src_compression="LZ4", dst_key=key_b, dst_compression=dc, verify=verify,
                       batch_bytes=batch, timestamp=2)
+            if a.stored:
+                records.append(stored_leg(a, name, leg, kw, packs, stored_packs, nblobs, torch, sync))
+                print(json.dumps(records[-1]), flush=True)
+                continue
             session = sync.SyncSession(**kw)
             native = sync.SyncPipeline(packers=a.packers, **kw)
             for p in packs:
@@ -147,7 +204,8 @@ def pipeline(a):
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            json.dump(dict(tool="tools/sync_bench.py --pipeline", records=records), f, indent=1)
+            json.dump(dict(tool="tools/sync_bench.py --pipeline" + (" --stored" if a.stored else ""), records=records), f,
+                      indent=1)
             f.write("\n")
 
 
@@ -158,6 +216,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--settings", default=",".join(SETTINGS))
     ap.add_argument("--pipeline", action="store_true", help="whole syncs: SyncSession against the native pipeline")
+    ap.add_argument("--stored", action="store_true",
+                    help="--pipeline: the native pipeline stored -> stored beside plain -> plain")
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--batch-mib", type=int, default=16, help="--pipeline: stored bytes per batch, both routes")
     ap.add_argument("--packers", type=int, default=0, help="--pipeline: the native run's packer threads (0: 8)")
@@ -166,6 +226,10 @@ def main():
     a = ap.parse_args()
     if a.reps < 3:
         ap.error("at least 3 repetitions: the spread is part of the result")
+    if a.stored and not a.pipeline:
+        ap.error("--stored goes with --pipeline")
+    if a.stored and a.out == ap.get_default("out"):
+        a.out = ""  # the default file holds the SyncSession comparison
     if a.pipeline:
         if a.reps < 5:
             ap.error("--pipeline: at least 5 repetitions of each route")
