@@ -13,6 +13,21 @@
  * status: CDC_OK / CDC_EOF / CDC_NEED_DATA (>= 0) or a negative CDC_E_* code.
  * cdc_strerror() turns a status into text.
  *
+ * Streams.  Every device entry point takes the caller's stream and states one
+ * of two contracts.  "Synchronous on `stream`": all device work is ordered
+ * after what `stream` already holds, and the call returns once that work has
+ * finished and `stream` is drained, so device outputs may be read from any
+ * stream and host outputs are final.  "Asynchronous on `stream`": the call
+ * enqueues its work in stream order and returns without waiting for what the
+ * stream holds (it may wait for an earlier call of its own whose table slot it
+ * takes again); the outputs are ready for work enqueued on `stream` after it.
+ * Either way the call waits for no other stream of the caller, and the host
+ * arrays passed in (offsets, lengths, segment and record tables, keys, random
+ * bytes) may be reused as soon as it returns: they are copied into pinned
+ * staging, or passed as kernel arguments, before that.  Side streams and
+ * events of the library's own are forked from and joined back to `stream`
+ * inside the call.
+ *
  * The product never falls back to the CPU.  If no GPU is present, or the HIP
  * runtime fails, calls return CDC_E_DEVICE / CDC_E_NO_DEVICE.
  */
@@ -204,7 +219,7 @@ int cdc_encode_device(int device, const void *d_base, const uint64_t *offsets, c
 /* cdc_encode_device at `level` (compression/compression.go:12-51): the level
  * changes which matches the LZ4 frame's sequences or the gzip member's blocks
  * hold, so the bytes and their count, nothing else.  cdc_encode_device is this
- * call with CDC_LEVEL_FAST. */
+ * call with CDC_LEVEL_FAST.  Synchronous on `stream`. */
 int cdc_encode_device_level(int device, const void *d_base, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                             int compress, const uint8_t *key, const uint8_t *random, uint8_t *d_out, uint64_t out_cap,
                             uint64_t *out_offsets, int level, void *stream);
@@ -298,7 +313,7 @@ int cdc_zip_pieces_device(int device, const void *d_src, uint64_t src_cap, const
 /* cdc_zip_pieces_device at `level` (compression/compression.go:12-51; CDC_LEVEL_*
  * above): with CDC_LEVEL_WIDE a match reaches up to 32,768 bytes back inside
  * its piece, never into another piece.  cdc_zip_pieces_device is this call
- * with CDC_LEVEL_FAST. */
+ * with CDC_LEVEL_FAST.  Synchronous on `stream`. */
 int cdc_zip_pieces_device_level(int device, const void *d_src, uint64_t src_cap, const cdc_zip_piece *pieces, uint32_t n,
                                 const uint8_t *hdr_arena, uint64_t hdr_arena_len, uint8_t *d_out, uint64_t out_cap,
                                 cdc_zip_piece_out *outs, uint64_t *total, int level, void *stream);
@@ -404,7 +419,8 @@ int cdc_decode_prefix_device(int device, const void *d_in, const uint64_t *offse
  * the capacity to retry with), hashes every blob that decoded with the
  * SHA-256 kernels of cdc_chunk_digests_device_async (so cdc_init must have
  * run) and compares with checksums (host, 32 bytes per blob) on the device.
- * status[i]: CDC_OK, CDC_E_MISMATCH, or blob i's decode error. */
+ * status[i]: CDC_OK, CDC_E_MISMATCH, or blob i's decode error.  Synchronous on
+ * `stream`. */
 int cdc_check_device(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                      int compressed, const uint8_t *key, const uint8_t *checksums, uint8_t *d_scratch,
                      uint64_t scratch_cap, uint64_t *needed, int32_t *status, void *stream);
@@ -484,7 +500,8 @@ int cdc_transcode_device(int device, const void *d_in, const uint64_t *offsets, 
  * (compression/compression.go:12-51; CDC_LEVEL_* above).  The re-key path, the
  * paths that only open, seal or copy, and a destination without compression
  * ignore it; a level that does not exist is CDC_E_INVALID on every path.
- * cdc_transcode_device is this call with CDC_LEVEL_FAST. */
+ * cdc_transcode_device is this call with CDC_LEVEL_FAST.  Synchronous on
+ * `stream`. */
 int cdc_transcode_device_level(int device, const void *d_in, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                                const cdc_codec *src, const cdc_codec *dst, const uint8_t *checksums,
                                const uint8_t *random, uint8_t *d_out, uint64_t out_cap, uint64_t *out_offsets,
@@ -1499,7 +1516,9 @@ int cdc_chunk_digests_device_async(int device, const void *d_data, uint64_t len,
  * time of a launch is that of its longest chunk, so batch).  d_results and
  * d_hist may be NULL; d_hist entries are all NULL or all set (a buffer with
  * cut_cap 0 may pass NULL either way).  Past 32 buffers the launch group
- * reads its descriptors from device memory (one launch, one tail). */
+ * reads its descriptors from device memory (one launch, one tail; the
+ * descriptors travel through a ring of 16 slots, and a call waits for the
+ * launch that last used the slot it takes).  Asynchronous on `stream`. */
 int cdc_chunk_digests_device_batch_async(int device, const void *const *d_data, const uint64_t *lens, int nbufs,
                                          const cdc_cut *const *d_cuts, const uint64_t *cut_caps,
                                          const cdc_result *const *d_results, uint8_t *const *d_digests,
@@ -1513,9 +1532,10 @@ int cdc_chunk_digests_device_batch_async(int device, const void *const *d_data, 
  * from the lengths (the longest chunks, as many as balance the host's bytes
  * over its cores and PCIe against the device's longest remaining chain);
  * otherwise every chunk of at least host_min_len bytes goes to the host.
- * host_threads = 0: all on the device.  Drains `stream` first (the cut lists
- * must be final) and returns once every digest and histogram is in device
- * memory; *host_chunks / *host_bytes (may be NULL) report the host's share.
+ * host_threads = 0: all on the device.  Synchronous on `stream`: drains it
+ * first (the cut lists must be final) and returns once every digest and
+ * histogram is in device memory, also when the host's share is empty;
+ * *host_chunks / *host_bytes (may be NULL) report the host's share.
  * At most 32 buffers. */
 int cdc_chunk_digests_hybrid(int device, const void *const *d_data, const uint64_t *lens, int nbufs,
                              const cdc_cut *const *d_cuts, const uint64_t *cut_caps, const cdc_result *const *d_results,

@@ -1189,11 +1189,16 @@ int cdc_chunk_digests_hybrid(int device, const void *const *d_data, const uint64
     DeviceCtx *ctx = nullptr;
     int st = check_ready(device, &ctx);
     if (st != CDC_OK) return st;
-    if (host_threads == 0 || nbufs == 0 || nbufs > kMaxBufsPerLaunch)  // all on the device
-        return cdc_chunk_digests_device_batch_async(device, d_data, lens, nbufs, d_cuts, cut_caps, d_results,
-                                                    d_digests, d_hist, stream);
     if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
     hipStream_t sm = reinterpret_cast<hipStream_t>(stream);
+    // all on the device: the batched form, then the drain that makes this call synchronous
+    auto all_on_device = [&]() -> int {
+        const int s2 = cdc_chunk_digests_device_batch_async(device, d_data, lens, nbufs, d_cuts, cut_caps, d_results,
+                                                            d_digests, d_hist, stream);
+        if (s2 != CDC_OK) return s2;
+        return hipStreamSynchronize(sm) == hipSuccess ? CDC_OK : CDC_E_DEVICE;
+    };
+    if (host_threads == 0 || nbufs == 0 || nbufs > kMaxBufsPerLaunch) return all_on_device();
     HybridScratch &H = hybrid_scratch(device);
     std::lock_guard<std::mutex> lk(H.mu);
     if (!H.side) {
@@ -1251,9 +1256,7 @@ int cdc_chunk_digests_hybrid(int device, const void *const *d_data, const uint64
         k = hybrid_split(sd, host_threads, 4);
     }
     while (k > 0 && L[order[k - 1]] == 0) --k;  // empty chunks stay on the device
-    if (k == 0)
-        return cdc_chunk_digests_device_batch_async(device, d_data, lens, nbufs, d_cuts, cut_caps, d_results,
-                                                    d_digests, d_hist, stream);
+    if (k == 0) return all_on_device();
     // the device's lists: the host's chunks as empty ones (their rows are overwritten below)
     std::vector<cdc_cut> mod(cuts);
     uint64_t hbytes = 0;

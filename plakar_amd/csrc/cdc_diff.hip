@@ -619,10 +619,10 @@ static int emit(int device, const uint8_t *d_plain, const uint8_t *d_lit, const 
     std::lock_guard<std::mutex> lk(S.mu);
     cdc::Carver c(16);
     const size_t o_recs = c.take(sizeof(cdc_emit_rec) * size_t(n)), o_units = c.take(sizeof(Unit) * units.size());
-    if (!S.h.reserve(c.bytes()) || !S.d.reserve(c.bytes())) return CDC_E_NOMEM;
-    // the scratch is reused only once the launch that read it has finished
+    // the scratch is reused, or freed to grow, only once the launch that read it has finished
     if (!S.ev && hipEventCreateWithFlags(&S.ev, hipEventDisableTiming) != hipSuccess) return CDC_E_DEVICE;
     if (S.used && hipEventSynchronize(S.ev) != hipSuccess) return CDC_E_DEVICE;
+    if (!S.h.reserve(c.bytes()) || !S.d.reserve(c.bytes())) return CDC_E_NOMEM;
     uint8_t *const h = S.h.as<uint8_t>(), *const d = S.d.as<uint8_t>();
     std::memcpy(h + o_recs, recs, sizeof(cdc_emit_rec) * size_t(n));
     std::memcpy(h + o_units, units.data(), sizeof(Unit) * units.size());
