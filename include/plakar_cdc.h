@@ -1577,6 +1577,125 @@ int cdc_chunker_new(const char *algorithm, cdc_read_fn read, void *ctx, const cd
 int cdc_chunker_next(cdc_chunker *c, const uint8_t **chunk, uint64_t *len);
 void cdc_chunker_free(cdc_chunker *c);
 
+/* ---- State: a repository's blob index, read, merged and queried on the device -----
+ * Every command opens the repository with RebuildState (repository/
+ * repository.go:58-164): it fetches every state file, Decodes and deserialises
+ * each (repository/state/state.go:235-348) and merges them into one aggregate
+ * (state.go:384-455) that answers BlobExists (:512), GetSubpartForBlob (:457),
+ * ListBlobs and ListSnapshots (:649-719).  A cdc_state is that aggregate, kept
+ * in device memory: what cdc_backup_opts.known, CDC_PACKFILE_ROWS and the
+ * sessions' locators are filled from.
+ *   A state file is Encode (PutState, repository.go:367-378) of what
+ * SerializeStream writes (state.go:132-233), all little endian:
+ *     u32 version | u64 timestamp ns | u8 aggregate | u64 n, n x 32 B extends
+ *     u64 n, n x (id u64, time u64)          DeletedSnapshots
+ *     u64 n, n x (id u64, checksum 32 B)     IdToChecksum, ids 0 .. n - 1 in any order
+ *     u64 n, n x (id u64, packfile id u64, offset u32, length u32)
+ *         for Chunks, Objects, Files, Directories, Children, Datas, Snapshots,
+ *         Signatures and Errors, in this order
+ * The smallest is 109 bytes; bytes after the last section are ignored and the
+ * version is not judged, as in DeserializeStream.
+ *   The merge rule is SetPackfileForBlob's (state.go:572-626): a (type,
+ * checksum) already present keeps its location.  Go ranges over maps, so the
+ * reference's winner among duplicates is arbitrary; here the state given first
+ * wins, among the states of one call and across calls, whatever the device's
+ * scheduling.  The reference reads a dangling id as the zero
+ * checksum; here a state with an IdToChecksum id >= its count or given twice,
+ * or a location or deleted-snapshot id with no checksum, is CDC_E_CORRUPT as a
+ * whole and nothing of it is entered. */
+#define CDC_STATE_PLAIN  0   /* the serialised bytes (SerializeStream) */
+#define CDC_STATE_STORED 1   /* what PutState stores: Encode of them */
+typedef struct cdc_state_src {
+    const uint8_t *bytes;    /* host memory, read during the call only */
+    uint64_t len;
+    uint8_t id[32];          /* the state's checksum (its name in the repository) */
+    int form;                /* CDC_STATE_* */
+} cdc_state_src;
+typedef struct cdc_state_row {
+    uint8_t checksum[32];    /* the blob */
+    uint8_t packfile[32];    /* the packfile that holds it */
+    uint32_t offset, length; /* of the encoded blob in the packfile */
+    uint8_t type;            /* packfile.TYPE_* (packfile/packfile.go:17-25): 0 snapshot, 1 chunk, 2 object, 3 file,
+                              * 4 directory, 5 child, 6 data, 7 signature, 8 error */
+    uint8_t found;           /* lookups: 1 when the state has the blob, else 0 and the location is zero */
+    uint8_t reserved[6];
+} cdc_state_row;             /* 80 bytes */
+typedef struct cdc_state_stats {
+    uint32_t struct_size;    /* set by the caller to sizeof(cdc_state_stats) */
+    uint32_t reserved;
+    uint64_t states, rejected;   /* sources entered, and sources whose status was not CDC_OK */
+    uint64_t rows[9];            /* by type: entries of the aggregate */
+    uint64_t deleted_snapshots;  /* distinct checksums in the merged states' DeletedSnapshots */
+    uint64_t capacity;           /* slots of the table; it holds at most capacity / 2 records */
+    uint64_t records;            /* location and deletion records entered so far, duplicates included */
+    uint64_t device_bytes;       /* held between calls: the records and the table */
+    double decode_s, index_s, insert_s;  /* summed over the merge calls */
+} cdc_state_stats;
+typedef struct cdc_state cdc_state;
+
+/* An empty aggregate on `device` for a repository with this compression
+ * (CDC_COMPRESS_*) and key (32 bytes, copied; NULL: not encrypted).  Needs no
+ * cdc_init.  CDC_E_INVALID for a NULL out or a device outside 0..63. */
+int cdc_state_new(int device, int compress, const uint8_t *key, cdc_state **out);
+void cdc_state_free(cdc_state *s);
+
+/* RebuildState's loop (repository.go:118-160) for n state files at once: every
+ * CDC_STATE_STORED source goes through one cdc_decode_device sizing-plus-decode
+ * together with the others, the plaintexts stay on the device, and three
+ * kernel stages run over all of them (no launch per state): the IdToChecksum
+ * records are scattered into per-state tables, every location becomes a
+ * record (type, checksums, offset, length), and the records are inserted.
+ * status[i] (host, n): CDC_OK, CDC_E_AUTH, CDC_E_CORRUPT, CDC_E_UNSUPPORTED (a
+ * decoded state of 4 GiB or more), or the Decode error.  Only CDC_OK states are
+ * entered, in source order, and their ids are appended to the extends list
+ * (Extends, repository.go:159).  May be called again: earlier states keep
+ * precedence; the table is rebuilt larger when the records pass half its
+ * slots.  Every record entered is kept (80 bytes), a duplicate's too: the table
+ * holds the winners.  Returns the call's own failure (CDC_E_INVALID: NULL
+ * arguments, an unknown form, a length without bytes; CDC_E_NOMEM: the
+ * aggregate is as before the call; CDC_E_DEVICE: free it), else CDC_OK.  Calls
+ * on one cdc_state are serialised by the library. */
+int cdc_state_merge(cdc_state *s, const cdc_state_src *srcs, uint32_t n, int32_t *status);
+
+/* GetSubpartForBlob (state.go:457-510) for n checksums (32 bytes each) of one
+ * type: out[i].checksum is the query, found 1 with the packfile's checksum,
+ * offset and length, or found 0 with zeros; BlobExists is `found`.  A snapshot
+ * named in DeletedSnapshots is still found, as in the reference.  The first
+ * form takes and fills host arrays; the second reads digests that already lie
+ * on the device (where cdc_chunk_digests_device_async leaves them) and writes
+ * device rows (d_out 16-byte aligned), asynchronously on `stream`; a merge on
+ * the same cdc_state must not run before that work is done.  CDC_E_INVALID for
+ * a NULL argument with n > 0, a misaligned d_out or a type above 8 (the
+ * reference panics), before the device is touched. */
+int cdc_state_lookup(cdc_state *s, uint8_t type, const uint8_t *checksums, uint64_t n, cdc_state_row *out);
+int cdc_state_lookup_device(cdc_state *s, uint8_t type, const uint8_t *d_checksums, uint64_t n, cdc_state_row *d_out,
+                            void *stream);
+
+/* ListBlobs (state.go:649-696) with the locations: the aggregate's rows of one
+ * type into rows[0, cap), in no particular order.  For type 0 the snapshots
+ * named in any merged state's DeletedSnapshots are left out, as ListSnapshots
+ * does (state.go:698-719).  With cap too small it returns CDC_E_NOSPACE,
+ * *needed (may be NULL) the count, and the first cap rows it found are set, as
+ * cdc_packfile_index has it. */
+int cdc_state_rows(cdc_state *s, uint8_t type, cdc_state_row *rows, uint64_t cap, uint64_t *needed);
+
+/* Metadata.Extends of the aggregate: the ids of the states entered, in order
+ * (32 bytes each).  CDC_E_NOSPACE and *needed as above. */
+int cdc_state_extends(cdc_state *s, uint8_t *ids, uint64_t cap, uint64_t *needed);
+int cdc_state_info(cdc_state *s, cdc_state_stats *stats);
+
+/* SerializeStream (state.go:132-216) for the delta Snapshot.Commit stores
+ * (snapshot/snapshot.go:325-334): the rows entered with SetPackfileForBlob in
+ * order (ids: the packfile's first, then the blob's, each checksum once; a row
+ * whose (type, checksum) was already seen is dropped), every section written
+ * in ascending id, no deleted snapshot.  `found` is ignored.  The result is
+ * 109 + 32 * nextends + 40 * ids + 24 * rows kept bytes; CDC_E_NOSPACE with *len
+ * set when cap is smaller.  Store it through cdc_encode_device.  Host only;
+ * needs no cdc_init.  CDC_E_INVALID: a NULL rows with n > 0, a NULL extends with
+ * nextends > 0, a NULL len, a type above 8. */
+int cdc_state_serialize(const cdc_state_row *rows, uint64_t n, int64_t timestamp_ns, int aggregate,
+                        const uint8_t *extends, uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len);
+
 /* ---- diagnostics ---------------------------------------------------------------
  * Kernel selection for tests: 0 = default (scan + index + speculative
  * resolution), 1 = force the sequential single-wave resolver (reference path
@@ -1617,6 +1736,12 @@ int cdc_debug_stream_read(int device, const void *d_buf, uint64_t len, int reps,
  * lanes on small inputs.  Digests never depend on it.  Not a reference
  * interface.  Returns CDC_OK. */
 int cdc_debug_set_digest_lanes(uint64_t lanes);
+
+/* The state kernels' grid: at most `blocks` workgroups per launch (0, the
+ * default, derives it from the device's CU count), so that a small test sends
+ * their grid-stride loops round more than once.  Results never depend on it.
+ * Not a reference interface.  Returns CDC_OK. */
+int cdc_debug_set_state_blocks(uint32_t blocks);
 
 /* Live profiling of the device path: when enabled, every launch group records
  * hipEvents on its stream before/after the scan kernel and after the last

@@ -146,6 +146,40 @@ class cdc_packfile_src(ctypes.Structure):
                 ("form", ctypes.c_int), ("rows", ctypes.POINTER(cdc_packfile_row)), ("nrows", ctypes.c_uint64)]
 
 
+# CDC_STATE_* of the header, without the prefix
+STATE_PLAIN, STATE_STORED = 0, 1
+
+
+def state_form_code(form):
+    """The C form for "plain" / "stored" (a state's serialised bytes, or what PutState stores); ValueError otherwise."""
+    try:
+        return {"plain": STATE_PLAIN, "stored": STATE_STORED}[form]
+    except (KeyError, TypeError):
+        raise ValueError(f"unsupported state form {form!r} (\"plain\" or \"stored\")") from None
+
+
+class cdc_state_src(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_void_p), ("len", ctypes.c_uint64), ("id", ctypes.c_uint8 * 32),
+                ("form", ctypes.c_int)]
+
+
+class cdc_state_row(ctypes.Structure):
+    _fields_ = [("checksum", ctypes.c_uint8 * 32), ("packfile", ctypes.c_uint8 * 32), ("offset", ctypes.c_uint32),
+                ("length", ctypes.c_uint32), ("type", ctypes.c_uint8), ("found", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 6)]
+
+
+STATE_ROW_DTYPE_FIELDS = [("checksum", "V32"), ("packfile", "V32"), ("offset", "<u4"), ("length", "<u4"),
+                          ("type", "u1"), ("found", "u1"), ("reserved", "V6")]
+
+
+class cdc_state_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("states", ctypes.c_uint64),
+                ("rejected", ctypes.c_uint64), ("rows", ctypes.c_uint64 * 9), ("deleted_snapshots", ctypes.c_uint64),
+                ("capacity", ctypes.c_uint64), ("records", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
+                ("decode_s", ctypes.c_double), ("index_s", ctypes.c_double), ("insert_s", ctypes.c_double)]
+
+
 class cdc_codec(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_char_p)]
 
@@ -564,6 +598,21 @@ SIGNATURES = {
     "cdc_debug_stream_read": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                              ctypes.c_double * 3, ctypes.c_double * 3, ctypes.c_void_p]),
     "cdc_debug_set_digest_lanes": (ctypes.c_int, [ctypes.c_uint64]),
+    "cdc_debug_set_state_blocks": (ctypes.c_int, [ctypes.c_uint32]),
+    "cdc_state_new": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _P(ctypes.c_void_p)]),
+    "cdc_state_free": (None, [ctypes.c_void_p]),
+    "cdc_state_merge": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_state_src), ctypes.c_uint32, _P(ctypes.c_int32)]),
+    "cdc_state_lookup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                        ctypes.c_void_p]),
+    "cdc_state_lookup_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "cdc_state_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                      _P(ctypes.c_uint64)]),
+    "cdc_state_extends": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_state_info": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_state_stats)]),
+    "cdc_state_serialize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           _P(ctypes.c_uint64)]),
     "cdc_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "cdc_profile_collect": (ctypes.c_int, [_P(ctypes.c_double), _P(ctypes.c_double),
                                            _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),

@@ -28,6 +28,35 @@ class Repository:
         return chunkers.NewChunker(c.Algorithm.lower(), rd, chunkers.ChunkerOpts(
             MinSize=int(c.MinSize), NormalSize=int(c.NormalSize), MaxSize=int(c.MaxSize)))
 
+    def RebuildState(self, states, ids=None, key=None, compression="LZ4", form="stored", device=0):
+        """repository/repository.go:58-164: merge the repository's state files
+        (bytes as stored, named by ids) into the aggregate the queries below
+        answer from.  Called again, it adds states to the same aggregate, as
+        the reference fetches only the states its cache lacks.  Returns the
+        per-state statuses (state.State.merge)."""
+        from . import state
+        if getattr(self, "_state", None) is None:
+            self._state = state.State(key=key, compression=compression, device=device)
+        return self._state.merge(states, ids=ids, form=form)
+
+    def State(self):
+        """The aggregate (state.State) RebuildState built; ValueError before it ran."""
+        if getattr(self, "_state", None) is None:
+            raise ValueError("RebuildState has not run")
+        return self._state
+
+    def BlobExists(self, type, checksums):
+        """repository.go:468-475 over state.BlobExists, for many checksums at once."""
+        return self.State().blob_exists(type, checksums)
+
+    def GetSubpartForBlob(self, type, checksums):
+        """state.GetSubpartForBlob as repository.go:449-466 calls it, for many checksums."""
+        return self.State().get_subpart_for_blob(type, checksums)
+
+    def ListSnapshots(self):
+        """repository.go:477-484 over state.ListSnapshots."""
+        return self.State().list_snapshots()
+
 
 def chunkify_lengths(repo: Repository, size: int, rd):
     """snapshot/backup.go:631-666: the chunk lengths plakar records for a file of

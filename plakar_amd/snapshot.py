@@ -498,7 +498,8 @@ from .restore import RestoreSession, SnapshotFile, read_ranges, restore_files  #
 from .check import CheckSession, check_files  # noqa: E402 - and the check of what was written
 from .diff import DiffSession, diff_files  # noqa: E402 - and the diff of two versions of it
 from .sync import SyncPipeline, sync_packfiles  # noqa: E402 - and its packfiles as another repository's
+from .state import State, delta_from_packfiles  # noqa: E402 - and the state Commit stores for them (snapshot.go:325-334)
 
 __all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
            "RestoreSession", "restore_files", "read_ranges", "SnapshotFile", "CheckSession", "check_files", "DiffSession",
-           "diff_files", "SyncPipeline", "sync_packfiles"]
+           "diff_files", "SyncPipeline", "sync_packfiles", "State", "delta_from_packfiles"]
