@@ -1696,6 +1696,121 @@ int cdc_state_info(cdc_state *s, cdc_state_stats *stats);
 int cdc_state_serialize(const cdc_state_row *rows, uint64_t n, int64_t timestamp_ns, int aggregate,
                         const uint8_t *extends, uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len);
 
+/* ---- Maintenance: rm and cleanup on the aggregate ----------------
+ * State.DeleteSnapshot (state.go:628-647) for n snapshots (32 bytes each):
+ * status[i] (host, n) is CDC_OK, or CDC_E_NOTFOUND when the aggregate has no
+ * snapshot row for the checksum (the reference's "snapshot not found").  Each
+ * one found gets a deletion record in the record store, entered into the table
+ * like a DeletedSnapshots record read from a state file: cdc_state_rows of type
+ * 0 leaves it out from then on and cdc_state_stats.deleted_snapshots counts
+ * it.  time_ns is kept with the record; the delta that makes the deletion
+ * durable is cdc_state_serialize_deleted's.  CDC_E_INVALID before the device
+ * is touched for a NULL argument with n > 0. */
+int cdc_state_delete_snapshots(cdc_state *s, const uint8_t *checksums, uint64_t n, int64_t time_ns, int32_t *status);
+
+/* cdc_state_serialize with a DeletedSnapshots section (state.go:176-184):
+ * ndeleted checksums (32 bytes each) with their times.  Their ids are given
+ * after the rows' ids (a checksum a row already named keeps that id), a
+ * checksum given twice keeps its last time, and the section is written in
+ * ascending id, 16 bytes per snapshot on top of cdc_state_serialize's size.
+ * With ndeleted = 0 the bytes are cdc_state_serialize's.  CDC_E_INVALID also
+ * for a NULL deleted or deleted_ns with ndeleted > 0.  Host only. */
+int cdc_state_serialize_deleted(const cdc_state_row *rows, uint64_t n, const uint8_t *deleted, const int64_t *deleted_ns,
+                                uint64_t ndeleted, int64_t timestamp_ns, int aggregate, const uint8_t *extends,
+                                uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len);
+
+/* Step 1 of cleanup (cmd/plakar/subcommands/cleanup/cleanup.go:35-45, "find
+ * which blobs the remaining snapshots use"): mark the aggregate's rows that
+ * the given references name.  refs: n records of 33 bytes, the type byte then
+ * the checksum (the format of cdc_sync_opts.known), in any order, duplicates
+ * welcome: what Snapshot.ListChunks, ListObjects, ListFiles, ListDirectories
+ * and ListDatas yield (snapshot/snapshot.go:348-428) for every snapshot kept.
+ * A reference the aggregate has marks its key's winning record (the row
+ * cdc_state_lookup answers with) and gets found[i] = 1; one it does not have,
+ * under this type, marks nothing and gets found[i] = 0.  found (n bytes) may
+ * be NULL; *missing (may be NULL) is the count of zeros.  The device form
+ * takes n digests of one type where cdc_chunk_digests_device_async left them
+ * and is asynchronous on `stream`, under cdc_state_lookup_device's promise;
+ * d_found (n bytes of device memory) may be NULL.  While such work is pending
+ * on a caller's stream, none of the calls that write the table or that zero or
+ * reallocate the bitmap may run on the same cdc_state (they drain only the
+ * aggregate's own stream): cdc_state_merge, cdc_state_delete_snapshots,
+ * cdc_state_clear_marks, and the first cdc_state_mark, cdc_state_mark_device
+ * or cdc_state_sweep after a merge or a deletion grew the record store (it
+ * grows the bitmap); a sweep also reads the marks, so it wants the work done
+ * in any case.  Marks accumulate over calls,
+ * and over cdc_state_merge and cdc_state_delete_snapshots, until
+ * cdc_state_clear_marks.  CDC_E_INVALID before the device is touched: a NULL
+ * s, a NULL refs with n > 0, a type above 8 (of any record: then nothing is
+ * marked). */
+int cdc_state_mark(cdc_state *s, const uint8_t *refs, uint64_t n, uint8_t *found, uint64_t *missing);
+int cdc_state_mark_device(cdc_state *s, uint8_t type, const uint8_t *d_checksums, uint64_t n, uint8_t *d_found,
+                          void *stream);
+int cdc_state_clear_marks(cdc_state *s);
+
+/* Steps 2 to 5 of cleanup's comment (cleanup.go:35-45) as a plan: which rows
+ * stay, which packfiles go, which are rewritten.  A record of the store (type
+ * 0..8, of a state that was entered) is LIVE when it is its key's winner in
+ * the table, and its mark is set or bit `type` of keep_types is, and, for a
+ * snapshot, no deletion names its checksum.  Every other record is dead: the
+ * unmarked, the deleted, and every loser, that is, the same blob entered again
+ * by a later state at another place or at the same one.
+ *   Per packfile (the 32 bytes a record names): extent = the largest offset +
+ * length (u64) over all its records, dead ones too; live_rows and live_bytes
+ * over its live records.  Verdict: DROP when live_rows == 0; REPACK when
+ * live_bytes * 1000 < extent * repack_permille; else KEEP.
+ *   The plan: the packfiles, ascending in first_record (the lowest record
+ * number that names each); kept rows, the live rows of KEEP packfiles in
+ * record-number order; repack rows, the live rows of REPACK packfiles grouped
+ * by packfile in the list's order and ascending in offset, [row_first,
+ * row_first + row_count) being one packfile's.  The same aggregate and marks
+ * give the same plan, byte for byte, whatever the device's scheduling.
+ *   cdc_state_sweep reads the aggregate and changes nothing in it; it runs on
+ * the aggregate's stream and is synchronous.  opts NULL: the defaults.
+ * CDC_E_INVALID before the device is touched: NULL s or out, a struct_size
+ * that is not this header's, repack_permille above 1000, a keep_types bit
+ * above 8.  An aggregate without records gives an empty plan.  The accessors
+ * follow cdc_state_rows: CDC_E_NOSPACE with *needed (may be NULL) the count
+ * and the first cap entries set. */
+#define CDC_SWEEP_KEEP   0
+#define CDC_SWEEP_DROP   1
+#define CDC_SWEEP_REPACK 2
+typedef struct cdc_sweep_opts {
+    uint32_t struct_size;     /* sizeof(cdc_sweep_opts) */
+    uint32_t keep_types;      /* bit t: rows of type t are live without a mark; default 1 << 0 (snapshots) */
+    uint32_t repack_permille; /* 0..1000; default 500 */
+    uint32_t reserved;
+} cdc_sweep_opts;
+typedef struct cdc_sweep_pack {
+    uint8_t packfile[32];
+    uint64_t extent;          /* max(offset + length) over every record that names it */
+    uint64_t live_bytes, live_rows;
+    uint64_t first_record;    /* the lowest record number that names it: the order of the list */
+    uint64_t row_first, row_count;  /* its slice of the repack rows (REPACK only, else 0, 0) */
+    int32_t verdict;          /* CDC_SWEEP_* */
+    uint32_t reserved;
+} cdc_sweep_pack;             /* 88 bytes */
+typedef struct cdc_sweep_stats {
+    uint32_t struct_size;     /* set by the caller to sizeof(cdc_sweep_stats) */
+    uint32_t reserved;
+    uint64_t records;         /* location records seen (type 0..8, of states that were entered) */
+    uint64_t live, dead;      /* live + dead == records */
+    uint64_t losers;          /* dead because another record holds the key */
+    uint64_t packs, keep, drop, repack;  /* packfiles, and how many got each verdict */
+    uint64_t kept_rows, repack_rows;
+    uint64_t live_bytes;         /* summed over all packfiles */
+    uint64_t reclaimable_bytes;  /* sum of extent - live_bytes over DROP and REPACK packfiles */
+    double packs_s, sweep_s, verdict_s, compact_s, download_s;  /* the four device stages, and the plan's way to the host */
+} cdc_sweep_stats;
+typedef struct cdc_sweep cdc_sweep;
+void cdc_sweep_default_opts(cdc_sweep_opts *opts);
+int cdc_state_sweep(cdc_state *s, const cdc_sweep_opts *opts, cdc_sweep **out);
+int cdc_sweep_packs(const cdc_sweep *p, cdc_sweep_pack *packs, uint64_t cap, uint64_t *needed);
+int cdc_sweep_kept_rows(const cdc_sweep *p, cdc_state_row *rows, uint64_t cap, uint64_t *needed);
+int cdc_sweep_repack_rows(const cdc_sweep *p, cdc_state_row *rows, uint64_t cap, uint64_t *needed);
+int cdc_sweep_info(const cdc_sweep *p, cdc_sweep_stats *stats);
+void cdc_sweep_free(cdc_sweep *p);
+
 /* ---- diagnostics ---------------------------------------------------------------
  * Kernel selection for tests: 0 = default (scan + index + speculative
  * resolution), 1 = force the sequential single-wave resolver (reference path

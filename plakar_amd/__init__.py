@@ -21,7 +21,11 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
                            packfiles registered in one call (add_packfiles on every session), packfile_index_stored
     plakar_amd.archive     a snapshot's entries as one tar or tar.gz stream (ArchiveSession, archive_files);
                            a gzip member written piece by piece on the device (GzipStream)
+    plakar_amd.state       the repository's blob index on the device (State: merge, lookup, rows, mark, sweep)
+    plakar_amd.maintenance rm and cleanup: the live set marked and swept on the device, the packfiles worth it
+                           rewritten through the sync pipeline (cleanup, SweepPlan, CleanupResult)
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "stored", "archive", "build"]
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "stored", "archive", "state",
+           "maintenance", "build"]

@@ -180,6 +180,33 @@ class cdc_state_stats(ctypes.Structure):
                 ("decode_s", ctypes.c_double), ("index_s", ctypes.c_double), ("insert_s", ctypes.c_double)]
 
 
+# CDC_SWEEP_* of the header, without the prefix
+SWEEP_KEEP, SWEEP_DROP, SWEEP_REPACK = 0, 1, 2
+
+
+class cdc_sweep_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("keep_types", ctypes.c_uint32), ("repack_permille", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class cdc_sweep_pack(ctypes.Structure):
+    _fields_ = [("packfile", ctypes.c_uint8 * 32), ("extent", ctypes.c_uint64), ("live_bytes", ctypes.c_uint64),
+                ("live_rows", ctypes.c_uint64), ("first_record", ctypes.c_uint64), ("row_first", ctypes.c_uint64),
+                ("row_count", ctypes.c_uint64), ("verdict", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+SWEEP_PACK_DTYPE_FIELDS = [("packfile", "V32"), ("extent", "<u8"), ("live_bytes", "<u8"), ("live_rows", "<u8"),
+                           ("first_record", "<u8"), ("row_first", "<u8"), ("row_count", "<u8"), ("verdict", "<i4"),
+                           ("reserved", "<u4")]
+
+
+class cdc_sweep_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(name, ctypes.c_uint64) for name in ("records", "live", "dead", "losers", "packs", "keep", "drop", "repack",
+                                                     "kept_rows", "repack_rows", "live_bytes", "reclaimable_bytes")] + \
+               [(name, ctypes.c_double) for name in ("packs_s", "sweep_s", "verdict_s", "compact_s", "download_s")]
+
+
 class cdc_codec(ctypes.Structure):
     _fields_ = [("compress", ctypes.c_int), ("key", ctypes.c_char_p)]
 
@@ -613,6 +640,23 @@ SIGNATURES = {
     "cdc_state_serialize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                            _P(ctypes.c_uint64)]),
+    "cdc_state_serialize_deleted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_state_delete_snapshots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64,
+                                                  _P(ctypes.c_int32)]),
+    "cdc_state_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                      _P(ctypes.c_uint64)]),
+    "cdc_state_mark_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "cdc_state_clear_marks": (ctypes.c_int, [ctypes.c_void_p]),
+    "cdc_sweep_default_opts": (None, [_P(cdc_sweep_opts)]),
+    "cdc_state_sweep": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_sweep_opts), _P(ctypes.c_void_p)]),
+    "cdc_sweep_packs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_sweep_kept_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_sweep_repack_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "cdc_sweep_info": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_sweep_stats)]),
+    "cdc_sweep_free": (None, [ctypes.c_void_p]),
     "cdc_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "cdc_profile_collect": (ctypes.c_int, [_P(ctypes.c_double), _P(ctypes.c_double),
                                            _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),

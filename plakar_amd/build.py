@@ -25,7 +25,7 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("cdc_internal.h", "cdc_hostme
                                                    "inflate_walk.h", "deflate_enc.h", "cdc_encode_dev.h", "restore_plan.h", "read_plan.h",
                                                    "transcode_plan.h", "archive_plan.h", "zip_plan.h", "cdc_locator.h", "check_plan.h",
                                                    "sha_blocks.h", "hybrid_model.h", "diff_plan.h", "sync_plan.h", "stored_plan.h", "cdc_stored.h",
-                                                   "state_plan.h", "cdc_state.h")] + \
+                                                   "state_plan.h", "cdc_state.h", "sweep_plan.h")] + \
           [os.path.join(ROOT, "include", "plakar_cdc.h")]
 ARCH = os.environ.get("PLAKAR_CDC_ARCH", "gfx950")
 

@@ -55,4 +55,43 @@ int launch_lookup(int device, const Table &T, uint32_t type, const uint8_t *d_su
 // d_n: one u64, zeroed here; rows past cap are counted and not written
 int launch_rows(int device, const Table &T, uint32_t type, cdc_state_row *d_out, uint64_t cap, uint64_t *d_n, void *stream);
 
+// ---- maintenance ----
+
+constexpr uint32_t kRefBytes = 33;   // a reference of cdc_state_mark: the type byte, then the checksum
+constexpr uint32_t kSweepTile = 256; // records per tile of the stable compaction: one trip of one workgroup
+
+// The packfile table and what a sweep accumulates beside it, all indexed by
+// the table's slot; P.recs is the record store, the key a record's packfile.
+struct Packs {
+    Table P;
+    uint64_t *extent, *live_bytes, *live_rows;
+    int32_t *verdict;
+};
+// Counters of a sweep, in device memory (zeroed by the host before the stage that adds to them).
+struct SweepCounts {
+    uint64_t packs;                // k_state_packs: slots claimed
+    uint64_t seen, live, losers;   // k_state_sweep
+    uint64_t listed;               // k_state_verdict: entries of the packfile list written
+    uint64_t kept, repack;         // k_sweep_scan: the totals of the two classes
+};
+
+// n references (stride 33 with the type in byte 0 when type == kTypeOfRecord,
+// else stride 32, all of `type`) -> bits of `marks`, found[i] when found is not null
+constexpr uint32_t kTypeOfRecord = 0xFFFFFFFFu;
+int launch_mark(int device, const Table &T, uint32_t type, const uint8_t *d_refs, uint64_t n, uint32_t *d_marks,
+                uint8_t *d_found, void *stream);
+// *d_missing (zeroed here) = the zeros among found[0, n)
+int launch_missing(int device, const uint8_t *d_found, uint64_t n, uint64_t *d_missing, void *stream);
+// the four stages of a sweep over records [0, nrecs); see cdc_state.hip
+int launch_packs(int device, const Table &P, uint64_t nrecs, SweepCounts *d_counts, void *stream);
+int launch_sweep(int device, const Table &T, const Packs &K, uint64_t nrecs, const uint32_t *d_marks, uint32_t keep_types,
+                 uint64_t *d_live, uint64_t *d_slot, SweepCounts *d_counts, void *stream);
+int launch_verdict(int device, const Packs &K, uint32_t permille, cdc_sweep_pack *d_list, uint64_t cap,
+                   SweepCounts *d_counts, void *stream);
+// d_class: one byte per record; d_tiles: 2 * (ntiles + 1) u64, counts then exclusive sums, kept at [2t], repack at [2t + 1]
+int launch_classes(int device, const Packs &K, uint64_t nrecs, const uint64_t *d_live, const uint64_t *d_slot,
+                   uint8_t *d_class, uint64_t *d_tiles, SweepCounts *d_counts, void *stream);
+int launch_compact(int device, const cdc_state_row *d_recs, uint64_t nrecs, const uint8_t *d_class, const uint64_t *d_tiles,
+                   cdc_state_row *d_kept, uint64_t kept_cap, cdc_state_row *d_repack, uint64_t repack_cap, void *stream);
+
 }  // namespace cst

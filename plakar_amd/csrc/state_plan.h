@@ -17,7 +17,8 @@
 // it multiplies or uses it, so no count can wrap and nothing is sized from one.
 // Bytes after the last section are ignored and the version is reported, not
 // judged, as DeserializeStream does (state.go:235-348).  The writer (Writer,
-// serialize) is SerializeStream for a list of rows.
+// serialize, serialize_deleted) is SerializeStream for a list of rows and of
+// deleted snapshots.
 //
 // No HIP, no library state: everything is a function of its arguments.  The
 // reader's functions carry SPLAN_FN, so that cdc_state.hip can compile the same
@@ -115,6 +116,7 @@ SPLAN_FN int read(const uint8_t *bytes, uint64_t len, Layout *L)
 
 #include <algorithm>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace splan {
@@ -146,6 +148,7 @@ struct Writer {
     std::vector<Sum> sums;                           // IdToChecksum
     std::vector<Loc> locs[kTypes];
     std::vector<uint8_t> seen[kTypes];               // by id: the type's map has it
+    std::unordered_map<uint64_t, int64_t> deleted;   // DeletedSnapshots: id -> time (ns)
 
     uint64_t id_of(const uint8_t *sum)  // getOrCreateIdForChecksum (state.go:118-130)
     {
@@ -167,13 +170,18 @@ struct Writer {
         locs[type].push_back(Loc{b, p, offset, length});
         return CDC_OK;
     }
+    // DeleteSnapshot (state.go:628-647) as a delta records it: the last time given stays
+    void delete_snapshot(const uint8_t *sum, int64_t time_ns) { deleted[id_of(sum)] = time_ns; }
     uint64_t rows() const
     {
         uint64_t n = 0;
         for (const auto &v : locs) n += v.size();
         return n;
     }
-    uint64_t size(uint64_t nextends) const { return kMinBytes + kSumBytes * nextends + kIdBytes * sums.size() + kLocBytes * rows(); }
+    uint64_t size(uint64_t nextends) const
+    {
+        return kMinBytes + kSumBytes * nextends + kDeletedBytes * deleted.size() + kIdBytes * sums.size() + kLocBytes * rows();
+    }
     // `out` holds size(nextends) bytes
     void write(int64_t timestamp_ns, int aggregate, const uint8_t *extends, uint64_t nextends, uint8_t *out)
     {
@@ -183,7 +191,10 @@ struct Writer {
         wr64(p, nextends), p += 8;
         if (nextends) memcpy(p, extends, size_t(kSumBytes * nextends));
         p += kSumBytes * nextends;
-        wr64(p, 0), p += 8;  // DeletedSnapshots: a delta of new rows deletes nothing
+        std::vector<std::pair<uint64_t, int64_t>> gone(deleted.begin(), deleted.end());
+        std::sort(gone.begin(), gone.end());
+        wr64(p, gone.size()), p += 8;
+        for (const auto &g : gone) wr64(p, g.first), wr64(p + 8, uint64_t(g.second)), p += kDeletedBytes;
         wr64(p, sums.size()), p += 8;
         for (uint64_t i = 0; i < sums.size(); ++i, p += kIdBytes) wr64(p, i), memcpy(p + 8, sums[i].b, 32);
         for (uint32_t s = kSecFirstType; s < kSections; ++s) {
@@ -198,20 +209,30 @@ struct Writer {
     }
 };
 
-// cdc_state_serialize without its NULL checks.
-static inline int serialize(const cdc_state_row *rows, uint64_t n, int64_t timestamp_ns, int aggregate,
-                            const uint8_t *extends, uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len)
+// cdc_state_serialize_deleted without its NULL checks: the rows, then the
+// deleted snapshots (their ids come after the rows').
+static inline int serialize_deleted(const cdc_state_row *rows, uint64_t n, const uint8_t *deleted, const int64_t *deleted_ns,
+                                    uint64_t ndeleted, int64_t timestamp_ns, int aggregate, const uint8_t *extends,
+                                    uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len)
 {
     Writer W;
     for (uint64_t i = 0; i < n; ++i) {
         const int st = W.set_packfile_for_blob(rows[i].type, rows[i].packfile, rows[i].checksum, rows[i].offset, rows[i].length);
         if (st != CDC_OK) return st;
     }
+    for (uint64_t i = 0; i < ndeleted; ++i) W.delete_snapshot(deleted + kSumBytes * i, deleted_ns[i]);
     if (nextends > (UINT64_MAX - W.size(0)) / kSumBytes) return CDC_E_INVALID;
     *len = W.size(nextends);
     if (*len > cap || !out) return CDC_E_NOSPACE;
     W.write(timestamp_ns, aggregate, extends, nextends, out);
     return CDC_OK;
+}
+
+// cdc_state_serialize without its NULL checks.
+static inline int serialize(const cdc_state_row *rows, uint64_t n, int64_t timestamp_ns, int aggregate,
+                            const uint8_t *extends, uint64_t nextends, uint8_t *out, uint64_t cap, uint64_t *len)
+{
+    return serialize_deleted(rows, n, nullptr, nullptr, 0, timestamp_ns, aggregate, extends, nextends, out, cap, len);
 }
 
 }  // namespace splan

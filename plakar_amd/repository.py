@@ -57,6 +57,24 @@ class Repository:
         """repository.go:477-484 over state.ListSnapshots."""
         return self.State().list_snapshots()
 
+    def DeleteSnapshot(self, checksum, when_ns=None):
+        """State.DeleteSnapshot (state.go:628-647) on the aggregate: `plakar
+        rm`.  KeyError("snapshot not found") as the reference's error.  The
+        caller stores the deletion with state.serialize_rows(deleted=...)."""
+        if self.State().delete_snapshots([bytes(checksum)], when_ns=when_ns)[0]:
+            raise KeyError("snapshot not found")
+
+    def Cleanup(self, live_refs, packfile_of, **opts):
+        """`plakar cleanup` (cleanup.go:35-45): live_refs are the (type,
+        checksum) pairs the remaining snapshots use; they replace whatever was
+        marked before.  Returns maintenance.cleanup's CleanupResult (key,
+        compression, packfile_form, ... in opts are the repository's)."""
+        from . import maintenance
+        S = self.State()
+        S.clear_marks()
+        S.mark(live_refs)
+        return maintenance.cleanup(S, packfile_of, **opts)
+
 
 def chunkify_lengths(repo: Repository, size: int, rd):
     """snapshot/backup.go:631-666: the chunk lengths plakar records for a file of

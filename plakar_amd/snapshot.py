@@ -499,7 +499,9 @@ from .check import CheckSession, check_files  # noqa: E402 - and the check of wh
 from .diff import DiffSession, diff_files  # noqa: E402 - and the diff of two versions of it
 from .sync import SyncPipeline, sync_packfiles  # noqa: E402 - and its packfiles as another repository's
 from .state import State, delta_from_packfiles  # noqa: E402 - and the state Commit stores for them (snapshot.go:325-334)
+from .maintenance import CleanupResult, SweepPlan, cleanup  # noqa: E402 - and what rm and cleanup make of that state
 
 __all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
            "RestoreSession", "restore_files", "read_ranges", "SnapshotFile", "CheckSession", "check_files", "DiffSession",
-           "diff_files", "SyncPipeline", "sync_packfiles", "State", "delta_from_packfiles"]
+           "diff_files", "SyncPipeline", "sync_packfiles", "State", "delta_from_packfiles", "cleanup",
+           "CleanupResult", "SweepPlan"]

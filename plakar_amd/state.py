@@ -17,6 +17,7 @@ with the state given first winning (the reference's order among duplicates is
 Go's map order).  Everything goes through the C ABI (cdc_state_*)."""
 import ctypes
 import hashlib
+import time
 
 import numpy as np
 
@@ -215,6 +216,92 @@ class State:
             out.setdefault(pack, []).append((typ, csum, off, ln))
         return out
 
+    def delete_snapshots(self, checksums, when_ns=None):
+        """cdc_state_delete_snapshots: State.DeleteSnapshot (state.go:628-647)
+        for many snapshots.  Returns the statuses: 0, or CDC_E_NOTFOUND for a
+        checksum the aggregate has no snapshot row for.  rows(TYPE_SNAPSHOT)
+        leaves the deleted ones out from then on; serialize_rows(deleted=...)
+        writes the delta that stores the deletion."""
+        q = _sums(checksums)
+        when = time.time_ns() if when_ns is None else int(when_ns)
+        status = (ctypes.c_int32 * max(len(q), 1))()
+        check(lib().cdc_state_delete_snapshots(self._handle(), q.ctypes.data, len(q), when, status),
+              "cdc_state_delete_snapshots")
+        return [int(status[i]) for i in range(len(q))]
+
+    def mark(self, refs):
+        """cdc_state_mark: mark the rows that `refs` name, (type, checksum)
+        pairs in any order, duplicates welcome (what a kept snapshot's
+        ListChunks, ListObjects, ... yield), or their 33-byte records as one
+        bytes object.  Returns (found, missing): a numpy bool array in the
+        order given, and the count of references the aggregate does not have.
+        Marks accumulate until clear_marks()."""
+        if isinstance(refs, (bytes, bytearray, memoryview)):
+            raw = bytes(refs)
+        else:
+            parts = []
+            for typ, csum in refs:
+                csum = bytes(csum)
+                if len(csum) != 32:
+                    raise ValueError("a checksum is 32 bytes (SHA-256)")
+                parts.append(bytes([_type(typ)]) + csum)
+            raw = b"".join(parts)
+        if len(raw) % 33:
+            raise ValueError("a reference is 33 bytes: the type, then the checksum")
+        n = len(raw) // 33
+        found = np.zeros(n, dtype=np.uint8)
+        missing = ctypes.c_uint64()
+        check(lib().cdc_state_mark(self._handle(), raw if n else None, n, found.ctypes.data if n else None,
+                                   ctypes.byref(missing)), "cdc_state_mark")
+        return found.astype(bool), int(missing.value)
+
+    def mark_device(self, type, digests, found=False, stream=None):
+        """cdc_state_mark_device: mark the rows of `type` that the digests
+        name, an (n, 32) uint8 CUDA tensor as hashing.chunk_digests returns
+        them.  Asynchronous on `stream` (default: the current stream).  With
+        found=True an (n,) uint8 CUDA tensor of 0/1 comes back, else None."""
+        import torch
+        typ = _type(type)
+        if digests.dtype != torch.uint8 or not digests.is_cuda or not digests.is_contiguous() or \
+                digests.dim() != 2 or digests.shape[1] != 32:
+            raise ValueError("expected a contiguous (n, 32) uint8 CUDA tensor")
+        n = digests.shape[0]
+        out = torch.empty(n, dtype=torch.uint8, device=digests.device) if found else None
+        if stream is None:
+            stream = torch.cuda.current_stream(digests.device)
+        check(lib().cdc_state_mark_device(self._handle(), typ, ctypes.c_void_p(digests.data_ptr()), n,
+                                          ctypes.c_void_p(out.data_ptr()) if found and n else None,
+                                          ctypes.c_void_p(stream.cuda_stream)), "cdc_state_mark_device")
+        return out
+
+    def clear_marks(self):
+        """cdc_state_clear_marks: forget every mark."""
+        check(lib().cdc_state_clear_marks(self._handle()), "cdc_state_clear_marks")
+
+    def sweep(self, keep_types=(TYPE_SNAPSHOT,), repack_permille=500):
+        """cdc_state_sweep: the plan of a cleanup (a SweepPlan) from the marks
+        set so far.  keep_types: the types whose rows are live without a mark
+        (an iterable, or the bit mask itself); repack_permille: a packfile
+        with live rows whose live bytes are below this many thousandths of
+        its extent is to be rewritten."""
+        o = _lib.cdc_sweep_opts()
+        lib().cdc_sweep_default_opts(ctypes.byref(o))
+        if isinstance(keep_types, int):
+            o.keep_types = keep_types
+        else:
+            o.keep_types = 0
+            for t in keep_types:
+                o.keep_types |= 1 << _type(t)
+        if not 0 <= int(repack_permille) <= 1000:
+            raise ValueError("repack_permille: 0..1000")
+        o.repack_permille = int(repack_permille)
+        h = ctypes.c_void_p()
+        check(lib().cdc_state_sweep(self._handle(), ctypes.byref(o), ctypes.byref(h)), "cdc_state_sweep")
+        try:
+            return SweepPlan._from_handle(h)
+        finally:
+            lib().cdc_sweep_free(h)
+
     def close(self):
         if self._h:
             lib().cdc_state_free(self._h)
@@ -233,10 +320,75 @@ class State:
             pass
 
 
-def serialize_rows(rows, timestamp_ns, aggregate=False, extends=()):
-    """cdc_state_serialize: SerializeStream of a state holding `rows`, an
-    iterable of (type, blob checksum, packfile checksum, offset, length),
-    entered in order with SetPackfileForBlob.  Host only."""
+PACK_DTYPE = np.dtype(_lib.SWEEP_PACK_DTYPE_FIELDS)
+assert PACK_DTYPE.itemsize == ctypes.sizeof(_lib.cdc_sweep_pack) == 88
+VERDICTS = {_lib.SWEEP_KEEP: "keep", _lib.SWEEP_DROP: "drop", _lib.SWEEP_REPACK: "repack"}
+
+
+class SweepPlan:
+    """What State.sweep found (cdc_sweep_*), copied to the host:
+
+    packs        PACK_DTYPE array, ascending in first_record
+    kept_rows    ROW_DTYPE array: the live rows of KEEP packfiles in
+                 record-number order
+    repack_rows  ROW_DTYPE array: the live rows of REPACK packfiles, grouped
+                 by packfile in the order of `packs`, ascending in offset;
+                 packs[i]'s are repack_rows[row_first : row_first + row_count]
+    info         cdc_sweep_stats as a dict"""
+
+    def __init__(self, packs, kept_rows, repack_rows, info):
+        self.packs, self.kept_rows, self.repack_rows, self.info = packs, kept_rows, repack_rows, info
+
+    @classmethod
+    def _from_handle(cls, h):
+        L = lib()
+
+        def fetch(fn, dtype):
+            need = ctypes.c_uint64()
+            rc = fn(h, None, 0, ctypes.byref(need))
+            out = np.zeros(need.value, dtype=dtype)
+            if rc == _lib.CDC_E_NOSPACE:
+                rc = fn(h, out.ctypes.data, len(out), ctypes.byref(need))
+            check(rc, "cdc_sweep")
+            return out
+
+        st = _lib.cdc_sweep_stats()
+        st.struct_size = ctypes.sizeof(st)
+        check(L.cdc_sweep_info(h, ctypes.byref(st)), "cdc_sweep_info")
+        info = {name: getattr(st, name) for name, _ in _lib.cdc_sweep_stats._fields_ if name not in ("struct_size", "reserved")}
+        return cls(fetch(L.cdc_sweep_packs, PACK_DTYPE), fetch(L.cdc_sweep_kept_rows, ROW_DTYPE),
+                   fetch(L.cdc_sweep_repack_rows, ROW_DTYPE), info)
+
+    def packfiles(self, verdict):
+        """The checksums of the packfiles with this verdict ("keep", "drop",
+        "repack" or a CDC_SWEEP_* value), in the list's order."""
+        code = {v: k for k, v in VERDICTS.items()}.get(verdict, verdict)
+        return _column(self.packs[self.packs["verdict"] == code], "packfile")
+
+    def repack_slices(self):
+        """[(packfile checksum, [(type, checksum, offset, length), ...])] of
+        the REPACK packfiles: add_packfiles(..., rows=...)'s shape."""
+        out = []
+        sums = _column(self.repack_rows, "checksum")
+        typ, off, ln = (self.repack_rows[k].tolist() for k in ("type", "offset", "length"))
+        for pack, v, first, count in zip(_column(self.packs, "packfile"), self.packs["verdict"].tolist(),
+                                         self.packs["row_first"].tolist(), self.packs["row_count"].tolist()):
+            if v == _lib.SWEEP_REPACK:
+                out.append((pack, [(typ[k], sums[k], off[k], ln[k]) for k in range(first, first + count)]))
+        return out
+
+
+def rows_as_tuples(rows):
+    """A ROW_DTYPE array as serialize_rows' (type, checksum, packfile, offset, length) tuples."""
+    return list(zip(rows["type"].tolist(), _column(rows, "checksum"), _column(rows, "packfile"), rows["offset"].tolist(),
+                    rows["length"].tolist()))
+
+
+def serialize_rows(rows, timestamp_ns, aggregate=False, extends=(), deleted=()):
+    """cdc_state_serialize_deleted: SerializeStream of a state holding `rows`,
+    an iterable of (type, blob checksum, packfile checksum, offset, length),
+    entered in order with SetPackfileForBlob, and the deleted snapshots
+    `deleted`, (checksum, time_ns) pairs.  Host only."""
     rows = list(rows)
     arr = np.zeros(len(rows), dtype=ROW_DTYPE)
     for k, (typ, csum, pack, off, ln) in enumerate(rows):
@@ -247,16 +399,21 @@ def serialize_rows(rows, timestamp_ns, aggregate=False, extends=()):
     ext = b"".join(bytes(e) for e in extends)
     if len(ext) % 32:
         raise ValueError("extends: 32-byte state ids")
+    deleted = [(bytes(c), int(t)) for c, t in deleted]
+    if any(len(c) != 32 for c, _ in deleted):
+        raise ValueError("a checksum is 32 bytes (SHA-256)")
+    gone = b"".join(c for c, _ in deleted)
+    times = np.array([t for _, t in deleted], dtype=np.int64)
     n = ctypes.c_uint64()
     L = lib()
-    args = (arr.ctypes.data if len(rows) else None, len(rows), int(timestamp_ns), int(bool(aggregate)), ext or None,
-            len(ext) // 32)
-    rc = L.cdc_state_serialize(*args, None, 0, ctypes.byref(n))
+    args = (arr.ctypes.data if len(rows) else None, len(rows), gone or None, times.ctypes.data if deleted else None,
+            len(deleted), int(timestamp_ns), int(bool(aggregate)), ext or None, len(ext) // 32)
+    rc = L.cdc_state_serialize_deleted(*args, None, 0, ctypes.byref(n))
     if rc == _lib.CDC_E_NOSPACE:
         out = ctypes.create_string_buffer(n.value)
-        check(L.cdc_state_serialize(*args, out, n.value, ctypes.byref(n)), "cdc_state_serialize")
+        check(L.cdc_state_serialize_deleted(*args, out, n.value, ctypes.byref(n)), "cdc_state_serialize_deleted")
         return out.raw[:n.value]
-    check(rc, "cdc_state_serialize")
+    check(rc, "cdc_state_serialize_deleted")
     return b""
 
 
