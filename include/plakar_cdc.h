@@ -1233,6 +1233,136 @@ int cdc_diff_files(cdc_diff *d, const cdc_diff_pair *pairs, int n, cdc_diff_pair
                    cdc_diff_stats *stats);
 void cdc_diff_free(cdc_diff *d);
 
+/* ---- grep: fixed strings in snapshot files -------------------------------------------
+ * `grep -F -e p0 -e p1 ... [-i] [-n] [-b] [-c] [-l] [-m]` over texts that lie in
+ * device memory.  The reference has no such command: its Snapshot.Search
+ * matches names, sizes and content types, never a file's bytes.
+ *
+ * Patterns: 1 to 32 fixed strings of 1 to 256 bytes; a pattern with the byte
+ * 0x0A is CDC_E_INVALID, every other byte (0x00 too) is ordinary; duplicates
+ * are allowed, each with its own bit and count.  CDC_GREP_IGNORE_CASE folds
+ * ASCII only: 'A'..'Z' equal 'a'..'z' and nothing else folds.
+ * Lines (grep's count): a text with k newline bytes has k lines when it ends in
+ * a newline or is empty, else k + 1; a line is the bytes between newlines (a
+ * '\r' before the newline belongs to it); numbers start at 1.
+ * Pattern k of m bytes occurs at column i of a line of len bytes when
+ * i + m <= len and the m bytes there equal the pattern after folding: an
+ * occurrence lies inside one line of one text, and no byte of a neighbouring
+ * text, of a gap between texts or outside them ever completes one.  A line
+ * with an occurrence yields one record: */
+#define CDC_GREP_IGNORE_CASE 1u
+typedef struct cdc_grep_hit {
+    uint32_t text;   /* index of the text (device entry point) or of the file in `files` (session) */
+    uint32_t line;   /* 1-based */
+    uint64_t off;    /* of the line's first byte: in the buffer (device entry point), in the file (session) */
+    uint32_t len;    /* without the newline */
+    uint32_t col;    /* the smallest column of any occurrence */
+    uint32_t mask;   /* bit k set: pattern k occurs in the line */
+    uint32_t nocc;   /* occurrences of all patterns, overlapping ones included; saturates at 2^32 - 1 */
+} cdc_grep_hit;
+
+/* Search n texts (text_off[i], text_len[i]: host arrays) of one device buffer.
+ * The texts ascend and do not overlap, at any alignment; a text is shorter
+ * than 4 GiB.  d_hits (device, 16-byte aligned, room for cap records) receives
+ * the records in text order, then line order, whatever the scheduling (every
+ * accumulator is an integer OR, add or min, and the compaction is stable by
+ * rank).  limit > 0: only the first `limit` matching lines of each text are
+ * written.  lines[i], matched[i], binary[i] (host, n each, may be NULL): the
+ * lines of text i, all its matching lines (limit or not), and 1 when it holds
+ * a 0x00 byte (grep's heuristic, for -I).  *total (may be NULL) = the records,
+ * the sum of min(matched, limit).  When cap is smaller: CDC_E_NOSPACE with
+ * lines, matched, binary and *total set and nothing written to d_hits.
+ * The line table is cdc_line_table_device's without the hashes; k_grep_scan
+ * then reads every byte of the texts once (and 255 bytes past each 16-KiB tile
+ * once more) and nothing else of the buffer: the work follows the texts, not
+ * len.  The worst case is bounded: a text of one byte value against 32
+ * patterns of 256 such bytes compares 8 KiB per position.
+ * Synchronous on `stream` (work ordered after the stream, which is drained at
+ * return; no other stream is waited for).
+ * CDC_E_INVALID before any HIP call: device outside 0..63, NULL arrays with a
+ * nonzero count, a text outside [0, len) or of 4 GiB or more, texts that do
+ * not ascend or that overlap, more than 2^32 - 2 lines possible, no pattern or
+ * more than 32, a pattern length outside 1..256, a newline in a pattern,
+ * unknown flag bits, d_hits NULL or misaligned with cap > 0; CDC_E_NOT_INIT
+ * before cdc_init; CDC_OK and nothing launched for n == 0. */
+int cdc_grep_device(int device, const void *d_data, uint64_t len, const uint64_t *text_off, const uint64_t *text_len,
+                    uint32_t n, const uint8_t *const *patterns, const uint32_t *pattern_len, uint32_t npatterns,
+                    uint32_t flags, uint64_t limit, cdc_grep_hit *d_hits, uint64_t cap, uint64_t *lines,
+                    uint64_t *matched, uint8_t *binary, uint64_t *total, void *stream);
+
+/* A grep context, shaped like a check context. */
+typedef struct cdc_grep_opts {
+    uint32_t struct_size;   /* sizeof(cdc_grep_opts) */
+    int compress;           /* CDC_COMPRESS_NONE, _LZ4 or _GZIP */
+    const uint8_t *key;     /* 32-byte repository key, or NULL */
+    int threads;            /* reader threads (0: 8) */
+    uint64_t batch_bytes;   /* of file bytes per batch (0: 256 MiB; at most 1 GiB) */
+    uint64_t max_lines;     /* per batch (0: 16 Mi) */
+} cdc_grep_opts;
+/* struct_size set, everything else 0. */
+void cdc_grep_default_opts(cdc_grep_opts *out);
+typedef struct cdc_grep_query {
+    uint32_t struct_size;   /* sizeof(cdc_grep_query) */
+    uint32_t flags;         /* CDC_GREP_IGNORE_CASE */
+    const uint8_t *const *patterns;
+    const uint32_t *pattern_len;
+    uint32_t npatterns;
+    uint64_t limit;         /* matching lines reported per file (0: 65,536) */
+    int want_text;          /* also return the matching lines' bytes */
+    uint32_t max_line_bytes;  /* of each line in the text (0: 4,096) */
+} cdc_grep_query;
+typedef struct cdc_grep_result {
+    int index;              /* position in files */
+    int status;             /* CDC_OK, CDC_E_NOTFOUND, CDC_E_NOSPACE, CDC_E_IO, CDC_E_MISMATCH or a blob's Decode error */
+    int64_t bad_chunk;      /* the chunk `status` names, or -1 */
+    int binary;             /* the file holds a 0x00 byte */
+    uint64_t size, lines, matched;  /* matched: all matching lines, limit or not; 0 for a file that failed */
+    const cdc_grep_hit *hits;       /* the first min(matched, limit), valid during the call */
+    uint64_t nhits;
+    const uint8_t *text;    /* want_text: per hit the line's first max_line_bytes bytes and "\n"; valid during the call */
+    uint64_t text_len;
+} cdc_grep_result;
+typedef struct cdc_grep_stats {
+    uint32_t struct_size;   /* set by the caller; at most that many bytes are written */
+    uint32_t reserved;
+    uint64_t files, failed_files, bytes, segments;  /* as cdc_check_stats */
+    uint64_t distinct_blobs, decoded_blobs, encoded_bytes, decoded_bytes, batches;
+    uint64_t lines, matched_lines, hits, occurrences, out_bytes;  /* occurrences: of the reported hits */
+    double read_s, h2d_s, decode_s, verify_s, assemble_s, table_s, scan_s, compact_s, emit_s, d2h_s;
+    double wall_s;
+} cdc_grep_stats;
+typedef void (*cdc_grep_file_fn)(void *ctx, const cdc_grep_result *r);
+typedef struct cdc_grep cdc_grep;
+/* CDC_E_INVALID: NULL, a struct_size that is not this header's, a device
+ * outside 0..63, an unknown compress, threads outside 0..256, batch_bytes over
+ * 1 GiB, max_lines over 2^31; CDC_E_NOT_INIT before cdc_init. */
+int cdc_grep_new(int device, const cdc_grep_opts *opts, cdc_grep **out);
+int cdc_grep_add_packfile(cdc_grep *g, const uint8_t *bytes, uint64_t len);  /* as cdc_restore_add_packfile */
+int cdc_grep_add_packfile_path(cdc_grep *g, const char *path);
+int cdc_grep_add_packfiles(cdc_grep *g, const cdc_packfile_src *srcs, uint32_t n, int32_t *status);  /* as cdc_restore_add_packfiles */
+/* Search n files from their chunk lists (object_checksum is not used).  The
+ * files go in batches of whole files of at most batch_bytes: reader threads
+ * gather the batch's distinct encoded blobs, one upload, one Decode with
+ * SHA-256 and compare over the distinct blobs (a blob many files share decodes
+ * once), the images laid out by cdc_assemble_device, then cdc_grep_device's
+ * stages over the images (groups of files of at most max_lines lines) and one
+ * copy back of the hit records, whose `text` is the file's index and `off` the
+ * line's offset in the file.  With want_text the lines are gathered by
+ * cdc_diff_emit_device and copied back once.  The stages of a batch run in
+ * sequence.  on_file (may be NULL) is called once per file from the calling
+ * thread, in file order.  Failures are per file and the run goes on:
+ * CDC_E_NOTFOUND with bad_chunk for a chunk in no packfile; a blob that cannot
+ * be read, fails Decode or has the wrong Length or SHA-256 fails every file
+ * that uses it (bad_chunk: the first such chunk) and no other; a file larger
+ * than batch_bytes or whose lines exceed max_lines fails alone with
+ * CDC_E_NOSPACE.  A file of 0 bytes has 0 lines and no hit and takes no device
+ * work.  Returns CDC_OK, or the run's own first failure; CDC_E_INVALID (NULL
+ * context, files or query, a query cdc_grep_device would refuse, a file with
+ * chunks and no arrays, stats->struct_size < 8) before the device is touched. */
+int cdc_grep_files(cdc_grep *g, const cdc_grep_query *q, const cdc_check_file *files, int n, cdc_grep_file_fn on_file,
+                   void *ctx, cdc_grep_stats *stats);
+void cdc_grep_free(cdc_grep *g);
+
 /* ---- sync: packfiles of one repository in, packfiles of another out ----------------
  * The loop of synchronize (cmd/plakar/subcommands/sync/sync.go:182-266): for
  * every blob the destination lacks, GetBlob from the source, PutBlob
@@ -1857,6 +1987,9 @@ int cdc_debug_set_digest_lanes(uint64_t lanes);
  * their grid-stride loops round more than once.  Results never depend on it.
  * Not a reference interface.  Returns CDC_OK. */
 int cdc_debug_set_state_blocks(uint32_t blocks);
+
+/* The same for the grep kernels (k_grep_scan and the passes after it). */
+int cdc_debug_set_grep_blocks(uint32_t blocks);
 
 /* Live profiling of the device path: when enabled, every launch group records
  * hipEvents on its stream before/after the scan kernel and after the last

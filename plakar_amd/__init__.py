@@ -15,6 +15,7 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
                            object_digests_device)
     plakar_amd.diff        unified diffs of pairs of files (DiffSession, diff_files; line_table_device,
                            line_ids_device, diff_script, diff_emit_device)
+    plakar_amd.grep        fixed strings in snapshot files, per matching line (GrepSession, grep_files; grep_device)
     plakar_amd.sync        blobs of one repository as blobs of another, on the device: re-key and
                            re-encode (transcode_device), synchronize()'s loop over packfiles (SyncSession)
     plakar_amd.stored      the form a repository keeps its packfiles in (snapshot.PutPackfile): many
@@ -27,5 +28,5 @@ include/plakar_cdc.h (libplakar_cdc.so), with Python mirrors of the Go API:
 """
 from . import chunking  # noqa: F401
 
-__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "sync", "stored", "archive", "state",
+__all__ = ["chunking", "chunkers", "repository", "device", "encode", "decode", "restore", "check", "diff", "grep", "sync", "stored", "archive", "state",
            "maintenance", "build"]

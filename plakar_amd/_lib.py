@@ -341,6 +341,40 @@ class cdc_diff_stats(ctypes.Structure):
 # CDC_DIFF_* and CDC_EMIT_* of the header, without the prefix: a module name that starts with CDC_ is a status code
 DIFF_EQUAL, DIFF_REPLACE, DIFF_DELETE, DIFF_INSERT = 0, 1, 2, 3
 EMIT_PREFIX, EMIT_LITERAL, EMIT_NEWLINE = 0x100, 0x200, 0x400
+GREP_IGNORE_CASE = 1
+
+
+class cdc_grep_hit(ctypes.Structure):
+    _fields_ = [("text", ctypes.c_uint32), ("line", ctypes.c_uint32), ("off", ctypes.c_uint64),
+                ("len", ctypes.c_uint32), ("col", ctypes.c_uint32), ("mask", ctypes.c_uint32),
+                ("nocc", ctypes.c_uint32)]
+
+
+class cdc_grep_opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("compress", ctypes.c_int), ("key", ctypes.c_void_p),
+                ("threads", ctypes.c_int), ("batch_bytes", ctypes.c_uint64), ("max_lines", ctypes.c_uint64)]
+
+
+class cdc_grep_query(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("patterns", ctypes.c_void_p),
+                ("pattern_len", ctypes.c_void_p), ("npatterns", ctypes.c_uint32), ("limit", ctypes.c_uint64),
+                ("want_text", ctypes.c_int), ("max_line_bytes", ctypes.c_uint32)]
+
+
+class cdc_grep_result(ctypes.Structure):
+    _fields_ = [("index", ctypes.c_int), ("status", ctypes.c_int), ("bad_chunk", ctypes.c_int64),
+                ("binary", ctypes.c_int), ("size", ctypes.c_uint64), ("lines", ctypes.c_uint64),
+                ("matched", ctypes.c_uint64), ("hits", ctypes.POINTER(cdc_grep_hit)), ("nhits", ctypes.c_uint64),
+                ("text", ctypes.POINTER(ctypes.c_uint8)), ("text_len", ctypes.c_uint64)]
+
+
+class cdc_grep_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("files", "failed_files", "bytes", "segments", "distinct_blobs",
+                                               "decoded_blobs", "encoded_bytes", "decoded_bytes", "batches", "lines",
+                                               "matched_lines", "hits", "occurrences", "out_bytes")] + \
+               [(n, ctypes.c_double) for n in ("read_s", "h2d_s", "decode_s", "verify_s", "assemble_s", "table_s",
+                                               "scan_s", "compact_s", "emit_s", "d2h_s", "wall_s")]
 
 
 class cdc_archive_opts(ctypes.Structure):
@@ -383,6 +417,7 @@ RESTORE_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_res
 READ_RANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_read_result))
 CHECK_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_check_result))
 DIFF_PAIR_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_diff_result))
+GREP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_grep_result))
 BACKUP_FILE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(cdc_backup_file))
 BACKUP_PACK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
 SYNC_BLOB_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint8, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int)
@@ -582,6 +617,21 @@ SIGNATURES = {
     "cdc_diff_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_diff_pair), ctypes.c_int, DIFF_PAIR_FN,
                                       ctypes.c_void_p, _P(cdc_diff_stats)]),
     "cdc_diff_free": (None, [ctypes.c_void_p]),
+    "cdc_grep_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint64),
+                                       _P(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p, _P(ctypes.c_uint32),
+                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
+                                       ctypes.c_uint64, _P(ctypes.c_uint64), _P(ctypes.c_uint64), _u8p,
+                                       _P(ctypes.c_uint64), ctypes.c_void_p]),
+    "cdc_debug_set_grep_blocks": (ctypes.c_int, [ctypes.c_uint32]),
+    "cdc_grep_default_opts": (None, [_P(cdc_grep_opts)]),
+    "cdc_grep_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_grep_opts), _P(ctypes.c_void_p)]),
+    "cdc_grep_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "cdc_grep_add_packfile_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "cdc_grep_add_packfiles": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_packfile_src), ctypes.c_uint32,
+                                   _P(ctypes.c_int32)]),
+    "cdc_grep_files": (ctypes.c_int, [ctypes.c_void_p, _P(cdc_grep_query), _P(cdc_check_file), ctypes.c_int,
+                                      GREP_FILE_FN, ctypes.c_void_p, _P(cdc_grep_stats)]),
+    "cdc_grep_free": (None, [ctypes.c_void_p]),
     "cdc_sync_default_opts": (None, [_P(cdc_sync_opts)]),
     "cdc_sync_new": (ctypes.c_int, [ctypes.c_int, _P(cdc_sync_opts), _P(ctypes.c_void_p)]),
     "cdc_sync_add_packfile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),

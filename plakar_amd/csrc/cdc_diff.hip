@@ -433,8 +433,11 @@ static uint32_t grid_for(int device, uint64_t waves)
     return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(blocks, uint64_t(cdc::device_cus(device)) * kBlocksPerCU)));
 }
 
+// room != NULL (cdc::line_table_raw): the records go where room(ctx, lines) says, once the count is known, and
+// k_line_hash does not run: a record then holds off, and in hash[0] the place of the line's end
 static int line_table(int device, const uint8_t *d_data, uint64_t data_len, const uint64_t *text_off, const uint64_t *text_len, uint32_t n,
-                      cdc_line_rec *d_recs, uint64_t cap, uint64_t *counts, uint64_t *total, hipStream_t st)
+                      cdc_line_rec *d_recs, uint64_t cap, uint64_t *counts, uint64_t *total, hipStream_t st,
+                      cdc::line_room_fn room = nullptr, void *room_ctx = nullptr)
 {
     if (hipSetDevice(device) != hipSuccess) return CDC_E_DEVICE;
     uint64_t ntiles64 = 0;
@@ -484,6 +487,11 @@ static int line_table(int device, const uint8_t *d_data, uint64_t data_len, cons
     if (counts) std::memcpy(counts, hcounts, 8 * size_t(n));
     if (total) *total = nlines;
     if (nlines > cap) return CDC_E_NOSPACE;
+    if (room) {
+        if (!(d_recs = room(room_ctx, nlines))) return CDC_E_NOMEM;
+        hipLaunchKernelGGL(k_line_mark, dim3(tgrid), dim3(kThreads), 0, st, d_data, dt, dtt, ntiles, dbase, d_recs, nlines);
+        return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? CDC_OK : CDC_E_DEVICE;
+    }
     if (!S.lst.reserve(4 * size_t(nlines))) return CDC_E_NOMEM;
     uint32_t *dlist = S.lst.as<uint32_t>();
     if (hipMemsetAsync(dlcnt, 0, 16, st) != hipSuccess) return CDC_E_DEVICE;
@@ -641,6 +649,13 @@ int cdc::line_ids(int device, const void *d_data, const cdc_line_rec *recs, uint
 {
     return dl::line_ids(device, static_cast<const uint8_t *>(d_data), recs, nlines, group, ngroups, hash_bits, ids, rounds,
                         reinterpret_cast<hipStream_t>(stream), threads);
+}
+
+int cdc::line_table_raw(int device, const void *d_data, uint64_t len, const uint64_t *text_off, const uint64_t *text_len, uint32_t n,
+                        uint64_t cap, line_room_fn room, void *ctx, uint64_t *counts, uint64_t *total, void *stream)
+{
+    return dl::line_table(device, static_cast<const uint8_t *>(d_data), len, text_off, text_len, n, nullptr, cap, counts, total,
+                          reinterpret_cast<hipStream_t>(stream), room, ctx);
 }
 
 extern "C" {

@@ -193,6 +193,22 @@ int object_digests(int device, const void *d_data, uint64_t len, const uint64_t 
 // threads, a group per task (the public call takes 8).
 int line_ids(int device, const void *d_data, const cdc_line_rec *recs, uint64_t nlines, const uint64_t *group,
              uint32_t ngroups, int hash_bits, uint32_t *ids, uint32_t *rounds, void *stream, int threads);
+// cdc_diff.hip: cdc_line_table_device after its argument checks and without the hashes, for the search
+// (cdc_grep.hip).  Once the lines are counted (counts, *total; CDC_E_NOSPACE when they exceed cap) the records
+// go where room(ctx, lines) says (NULL: CDC_E_NOMEM).  A record holds off, and in hash[0] the place of the
+// line's end in the buffer; len, reserved and hash[1] are not written.  Synchronous on `stream`.
+typedef cdc_line_rec *(*line_room_fn)(void *ctx, uint64_t nlines);
+int line_table_raw(int device, const void *d_data, uint64_t len, const uint64_t *text_off, const uint64_t *text_len, uint32_t n,
+                   uint64_t cap, line_room_fn room, void *ctx, uint64_t *counts, uint64_t *total, void *stream);
+// cdc_grep.hip: cdc_grep_device with the records where room(ctx, records) says once their number is known
+// (NULL: CDC_E_NOSPACE; not asked when there is none), for the grep pipeline too.  times (may be NULL): the
+// seconds of the line table, the scan and the passes after it are added to times[0..2].  CDC_E_INVALID as
+// cdc_grep_device; the caller has seen cdc_init.
+typedef cdc_grep_hit *(*grep_room_fn)(void *ctx, uint64_t records);
+int grep_texts(int device, const void *d_data, uint64_t len, const uint64_t *text_off, const uint64_t *text_len, uint32_t n,
+               const uint8_t *const *patterns, const uint32_t *pattern_len, uint32_t npatterns, uint32_t flags, uint64_t limit,
+               grep_room_fn room, void *ctx, uint64_t *lines, uint64_t *matched, uint8_t *binary, uint64_t *total, void *stream,
+               double *times);
 double host_sha256_rate();  // cdc_api.cpp: one host core's SHA-256 bytes per second, measured once
 extern uint64_t g_digest_lanes;
 // The calling thread's scan mode for make_plan: -1 the default (static grid,

@@ -497,11 +497,12 @@ def backup_files(paths, repo: Repository = None, key=None, compression="LZ4", kn
 from .restore import RestoreSession, SnapshotFile, read_ranges, restore_files  # noqa: E402 - the read path, next to backup_files
 from .check import CheckSession, check_files  # noqa: E402 - and the check of what was written
 from .diff import DiffSession, diff_files  # noqa: E402 - and the diff of two versions of it
+from .grep import GrepSession, grep_files  # noqa: E402 - and the search inside its files
 from .sync import SyncPipeline, sync_packfiles  # noqa: E402 - and its packfiles as another repository's
 from .state import State, delta_from_packfiles  # noqa: E402 - and the state Commit stores for them (snapshot.go:325-334)
 from .maintenance import CleanupResult, SweepPlan, cleanup  # noqa: E402 - and what rm and cleanup make of that state
 
 __all__ = ["Object", "ChunkRecords", "route", "chunkify_batch", "backup_batch", "BackupSession", "backup_files",
            "RestoreSession", "restore_files", "read_ranges", "SnapshotFile", "CheckSession", "check_files", "DiffSession",
-           "diff_files", "SyncPipeline", "sync_packfiles", "State", "delta_from_packfiles", "cleanup",
+           "diff_files", "GrepSession", "grep_files", "SyncPipeline", "sync_packfiles", "State", "delta_from_packfiles", "cleanup",
            "CleanupResult", "SweepPlan"]
