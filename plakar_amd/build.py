@@ -21,12 +21,13 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in ("cdc_kernels.hip", "cdc_diges
                                                     "cdc_restore.hip", "cdc_restore.cpp", "cdc_transcode.hip",
                                                     "cdc_archive.cpp", "cdc_check.cpp", "cdc_diff.hip", "cdc_diff.cpp",
                                                     "cdc_sync.cpp", "cdc_stored.cpp", "cdc_state.hip", "cdc_state.cpp",
-                                                    "cdc_grep.hip", "cdc_grep.cpp")]
+                                                    "cdc_grep.hip", "cdc_grep.cpp", "cdc_blobsrc.cpp", "cdc_reader.cpp")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("cdc_internal.h", "cdc_hostmem.h", "cdc_crypto_dev.h", "lz4_walk.h",
                                                    "inflate_walk.h", "deflate_enc.h", "cdc_encode_dev.h", "restore_plan.h", "read_plan.h",
                                                    "transcode_plan.h", "archive_plan.h", "zip_plan.h", "cdc_locator.h", "check_plan.h",
                                                    "sha_blocks.h", "hybrid_model.h", "diff_plan.h", "sync_plan.h", "stored_plan.h", "cdc_stored.h",
-                                                   "state_plan.h", "cdc_state.h", "sweep_plan.h", "grep_plan.h")] + \
+                                                   "state_plan.h", "cdc_state.h", "sweep_plan.h", "grep_plan.h", "cdc_hostutil.h", "cdc_blobsrc.h",
+                                                   "cdc_reader.h")] + \
           [os.path.join(ROOT, "include", "plakar_cdc.h")]
 ARCH = os.environ.get("PLAKAR_CDC_ARCH", "gfx950")
 

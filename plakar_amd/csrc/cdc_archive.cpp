@@ -8,11 +8,12 @@
 // gzip.NewWriter.  Here the tar stream is planned up front (archive_plan.h) in
 // batches of stream bytes, and a batch goes through
 //
-//   read      its distinct encoded blobs, gathered into a pinned arena
-//             (memcpy or pread, on `writers` threads) with the batch's header
-//             blocks and a zero block behind them;
+//   read      its distinct encoded blobs gathered (cdc_reader.h: gather_read,
+//             on `writers` threads) with the batch's header blocks and a zero
+//             block behind them;
 //   H2D       one copy of each;
-//   Decode    (+ verify) over the distinct blobs, as restore's;
+//   Decode    the shared decode step (+ verify) over the distinct blobs
+//             (cdc_reader.h: decode_batch);
 //   assemble  cdc_assemble_device: chunk occurrences, header blocks and
 //             padding into the batch's image of the tar stream;
 //   deflate   tar.gz: cdc_gzip_stream_piece over the image, one member for
@@ -38,63 +39,36 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "archive_plan.h"
-#include "cdc_hostmem.h"
-#include "cdc_internal.h"
-#include "cdc_locator.h"
-#include "cdc_stored.h"
+#include "cdc_reader.h"
 #include "deflate_enc.h"
 #include "inflate_walk.h"
 #include "zip_plan.h"
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
-
-template <class F>
-static void parallel_for(int threads, size_t n, F fn)
-{
-    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
-    if (t <= 1) {
-        for (size_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
+using cdc::Clock;
+using cdc::since;
 
 constexpr uint64_t kMaxBatch = 1ull << 30;  // a batch's image is one gzip piece: under 2 GiB with its largest chunk
 
 }  // namespace
 
 struct cdc_archive {
-    int device = 0;
+    cdc::PackSource src;  // device, codec, locator, run lock
     cdc_archive_opts o{};
     bool zip = false;  // cdc_archive_new_zip: o.format is not read
     int level = CDC_LEVEL_FAST;  // cdc_archive_set_level: the match search of tar.gz and zip
-    std::vector<uint8_t> key;
-    cdc::Locator loc;
     hipStream_t stream = nullptr;
-    cdc::PinBuf h_in, h_out;
-    cdc::DevBuf d_in, d_plain, d_img, d_gz;
-    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_archive_add_packfiles)
-    std::mutex run_mu;
+    cdc::Arena in;  // the batch's encoded blobs, its header blocks behind them in the pinned half
+    cdc::PinBuf h_out;
+    cdc::DevBuf d_plain, d_img, d_gz;
 };
 
 namespace {
@@ -122,49 +96,20 @@ struct Run {
 static int stage_image(Run &X, const aplan::Batch &B)
 {
     cdc_archive *A = X.A;
-    const cdc::Locator &L = A->loc;
+    const cdc::Locator &L = A->src.loc;
     const uint32_t nb = uint32_t(B.blobs.size());
     hipStream_t s = A->stream;
     // read
+    const uint64_t arena_base = cdc::align_up(B.plain_bytes, 16), plain_cap = arena_base + B.arena.size();
+    if (!A->d_plain.reserve(plain_cap) || !A->d_img.reserve(B.out_bytes)) return CDC_E_NOMEM;
+    cdc::Arena &I = A->in;
+    I.set_blobs(L, B.blobs.data(), nb);
+    int st = cdc::gather_read(L, I, A->o.writers, B.arena.size(), &X.st.read_s, &X.st.encoded_bytes);
+    if (st != CDC_OK) return st;
     auto t0 = Clock::now();
-    std::vector<uint64_t> eoff(nb), elen(nb);
-    std::vector<int32_t> pre(nb, CDC_OK);
-    uint64_t enc = 0;
-    std::unordered_map<uint32_t, int> fds;
-    for (uint32_t b = 0; b < nb; ++b) {
-        const cdc::Locator::Loc &l = L.locs[B.blobs[b].id];
-        eoff[b] = enc;
-        elen[b] = l.length;
-        enc += l.length;
-        const cdc::Locator::Pack &P = L.packs[l.pack];
-        if (!P.mem && !fds.count(l.pack)) fds[l.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-    }
-    const uint64_t h_arena = cdc::align_up(enc, 16), arena_base = cdc::align_up(B.plain_bytes, 16);
-    const uint64_t plain_cap = arena_base + B.arena.size();
-    auto close_fds = [&] {
-        for (auto &f : fds)
-            if (f.second >= 0) close(f.second);
-    };
-    if (!A->h_in.reserve(h_arena + B.arena.size()) || !A->d_in.reserve(enc) || !A->d_plain.reserve(plain_cap) ||
-        !A->d_img.reserve(B.out_bytes)) {
-        close_fds();
-        return CDC_E_NOMEM;
-    }
-    uint8_t *const h = A->h_in.as<uint8_t>();
-    parallel_for(A->o.writers, nb, [&](size_t b) {
-        const cdc::Locator::Loc &l = L.locs[B.blobs[b].id];
-        const cdc::Locator::Pack &P = L.packs[l.pack];
-        if (P.mem) {
-            std::memcpy(h + eoff[b], P.mem + l.offset, l.length);
-            return;
-        }
-        const int fd = fds.find(l.pack)->second;
-        if (fd < 0 || !cdc::pread_all(fd, h + eoff[b], l.length, l.offset)) pre[b] = CDC_E_IO;
-    });
-    close_fds();
-    if (!B.arena.empty()) std::memcpy(h + h_arena, B.arena.data(), B.arena.size());
+    uint8_t *const h_arena = I.h.as<uint8_t>() + cdc::align_up(I.total, 16);
+    if (!B.arena.empty()) std::memcpy(h_arena, B.arena.data(), B.arena.size());
     X.st.read_s += since(t0);
-    X.st.encoded_bytes += enc;
     // which entry a blob belongs to (its first use in the batch), for a failure's name
     auto blame = [&](uint32_t b, int status) {
         for (const aplan::Segment &S : B.segs)
@@ -175,50 +120,26 @@ static int stage_image(Run &X, const aplan::Batch &B)
         return status;
     };
     for (uint32_t b = 0; b < nb; ++b)
-        if (pre[b] != CDC_OK) return blame(b, pre[b]);
+        if (I.pre[b] != CDC_OK) return blame(b, I.pre[b]);
     // H2D
     t0 = Clock::now();
     uint8_t *const plain = A->d_plain.as<uint8_t>();
-    if ((enc && hipMemcpyAsync(A->d_in.data(), h, enc, hipMemcpyHostToDevice, s) != hipSuccess) ||
-        (!B.arena.empty() &&
-         hipMemcpyAsync(plain + arena_base, h + h_arena, B.arena.size(), hipMemcpyHostToDevice, s) != hipSuccess) ||
+    if ((I.total && hipMemcpyAsync(I.d.data(), I.h.data(), I.total, hipMemcpyHostToDevice, s) != hipSuccess) ||
+        (!B.arena.empty() && hipMemcpyAsync(plain + arena_base, h_arena, B.arena.size(), hipMemcpyHostToDevice, s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
         return CDC_E_DEVICE;
     X.st.h2d_s += since(t0);
-    // Decode (+ verify)
-    std::vector<uint64_t> oo(size_t(nb) + 1, 0);
-    std::vector<int32_t> bst(std::max<uint32_t>(nb, 1), CDC_OK);
-    std::vector<uint8_t> want;
-    if (A->o.verify) {
-        want.resize(size_t(nb) * 32 + 1);
-        for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], L.sums[B.blobs[b].id].b, 32);
-    }
-    const uint8_t *key = A->key.empty() ? nullptr : A->key.data();
-    const uint8_t *sums = A->o.verify ? want.data() : nullptr;
+    // Decode (+ verify): the first blob in batch order that is not right names the entry
+    cdc::Decoded D;
+    uint64_t decoded = 0;
+    D.set_blobs(A->o.verify != 0, L, B.blobs.data(), nb);
     if (nb) {
-        int st = cdc::decode_checked(A->device, A->d_in.data(), eoff.data(), elen.data(), nb, A->o.compress, key, sums, plain,
-                                     B.plain_bytes, oo.data(), bst.data(), s, &X.st.decode_s, &X.st.verify_s);
-        if (st == CDC_E_NOSPACE) {
-            // some blob decodes to more than its recorded Length: one by one, each
-            // into the room its Length gives it, to name it
-            for (uint32_t b = 0; b < nb; ++b) {
-                uint64_t o2[2] = {0, 0};
-                int32_t one = CDC_OK;
-                st = cdc::decode_checked(A->device, A->d_in.data(), &eoff[b], &elen[b], 1, A->o.compress, key,
-                                         sums ? sums + size_t(b) * 32 : nullptr, plain, B.blobs[b].len, o2, &one, s,
-                                         &X.st.decode_s, &X.st.verify_s);
-                if (st == CDC_E_NOSPACE) return blame(b, CDC_E_MISMATCH);
-                if (st != CDC_OK) return st;
-                if (one != CDC_OK) return blame(b, one);
-            }
-            return CDC_E_MISMATCH;
-        }
+        st = cdc::decode_batch(cdc::DecodeCtx{A->src.device, A->src.compress, A->src.key_ptr(), A->o.verify != 0, s}, I, plain,
+                               B.plain_bytes, D, cdc::DecodeTally{&decoded, &X.st.decode_s, &X.st.verify_s});
         if (st != CDC_OK) return st;
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (bst[b] != CDC_OK) return blame(b, bst[b]);
-            if (oo[b + 1] - oo[b] != B.blobs[b].len) return blame(b, CDC_E_MISMATCH);
-        }
-        X.st.decoded_bytes += oo[nb];
+        for (uint32_t b = 0; b < nb; ++b)
+            if (D.bst[b] != CDC_OK) return blame(b, D.bst[b]);
+        X.st.decoded_bytes += decoded;
     }
     // assemble
     t0 = Clock::now();
@@ -227,12 +148,12 @@ static int stage_image(Run &X, const aplan::Batch &B)
         std::vector<uint64_t> so(ns), sl(ns), sd(ns);
         for (size_t i = 0; i < ns; ++i) {
             const aplan::Segment &S = B.segs[i];
-            so[i] = S.arena ? arena_base + S.src_off : oo[S.blob];
+            so[i] = S.arena ? arena_base + S.src_off : D.pos[S.blob];
             sl[i] = S.len;
             sd[i] = S.dst_off;
         }
-        const int st = cdc_assemble_device(A->device, plain, plain_cap, so.data(), sl.data(), sd.data(), ns, A->d_img.data(),
-                                           B.out_bytes, s);
+        st = cdc_assemble_device(A->src.device, plain, plain_cap, so.data(), sl.data(), sd.data(), ns, A->d_img.data(),
+                                 B.out_bytes, s);
         if (st != CDC_OK) return st;
         if (hipStreamSynchronize(s) != hipSuccess) return CDC_E_DEVICE;
     }
@@ -300,16 +221,8 @@ static int run(cdc_archive *A, const cdc_archive_entry *entries, int n, const ch
         const bool dir = E.type == CDC_ARCHIVE_DIR;
         std::vector<uint32_t> ids(dir ? 0 : size_t(E.nchunks));
         uint64_t size = 0;
-        bool found = true;
-        for (uint64_t c = 0; c < ids.size() && found; ++c) {
-            cdc::Sum s;
-            std::memcpy(s.b, E.checksums + 32 * c, 32);
-            const auto it = A->loc.index.find(s);
-            found = it != A->loc.index.end();
-            if (found) ids[size_t(c)] = it->second;
-            size += E.lengths[c];
-        }
-        if (!found) {
+        for (uint64_t c = 0; c < ids.size(); ++c) size += E.lengths[c];
+        if (cdc::resolve(A->src.loc, E.checksums, ids.size(), ids.data()) >= 0) {
             ++X.st.skipped_entries;
             if (on_entry) on_entry(ctx, i, CDC_E_NOTFOUND);
             continue;
@@ -338,13 +251,13 @@ static int run(cdc_archive *A, const cdc_archive_entry *entries, int n, const ch
     }
     X.st.batches = batches.size();
     X.st.entries = X.pidx.size();
-    if (hipSetDevice(A->device) != hipSuccess) return finish(CDC_E_DEVICE);
+    if (hipSetDevice(A->src.device) != hipSuccess) return finish(CDC_E_DEVICE);
     if (path) {
         X.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
         if (X.fd < 0) return finish(CDC_E_IO);
     }
     cdc_gzip_stream *gz = nullptr;
-    int st = A->o.format == CDC_ARCHIVE_TARGZ ? cdc_gzip_stream_new(A->device, &gz) : CDC_OK;
+    int st = A->o.format == CDC_ARCHIVE_TARGZ ? cdc_gzip_stream_new(A->src.device, &gz) : CDC_OK;
     if (st == CDC_OK && gz) st = cdc_gzip_stream_set_level(gz, A->level);
     for (size_t k = 0; k < batches.size() && st == CDC_OK; ++k) st = run_batch(X, batches[k], gz, k + 1 == batches.size());
     cdc_gzip_stream_free(gz);
@@ -409,7 +322,7 @@ static int run_zip_batch(Run &X, const zplan::Batch &B, std::vector<zplan::Recor
     const uint64_t cap = zip_bound(B);
     uint64_t total = 0;
     if (!A->d_gz.reserve(cap)) return CDC_E_NOMEM;
-    st = cdc_zip_pieces_device_level(A->device, A->d_img.data(), B.a.out_bytes, pc.data(), uint32_t(np), B.hdrs.data(),
+    st = cdc_zip_pieces_device_level(A->src.device, A->d_img.data(), B.a.out_bytes, pc.data(), uint32_t(np), B.hdrs.data(),
                                      B.hdrs.size(), A->d_gz.as<uint8_t>(), cap, po.data(), &total, A->level, s);
     if (st != CDC_OK) {
         // a piece the pass cannot take (2 GiB or more): the entry is to blame
@@ -482,15 +395,7 @@ static int run_zip(cdc_archive *A, const cdc_archive_entry *entries, int n, cons
             continue;
         }
         std::vector<uint32_t> ids(size_t(E.nchunks));
-        bool found = true;
-        for (uint64_t c = 0; c < ids.size() && found; ++c) {
-            cdc::Sum s;
-            std::memcpy(s.b, E.checksums + 32 * c, 32);
-            const auto it = A->loc.index.find(s);
-            found = it != A->loc.index.end();
-            if (found) ids[size_t(c)] = it->second;
-        }
-        if (!found) {
+        if (cdc::resolve(A->src.loc, E.checksums, ids.size(), ids.data()) >= 0) {
             ++X.st.skipped_entries;
             if (on_entry) on_entry(ctx, i, CDC_E_NOTFOUND);
             continue;
@@ -520,7 +425,7 @@ static int run_zip(cdc_archive *A, const cdc_archive_entry *entries, int n, cons
     }
     X.st.batches = batches.size();
     X.st.entries = X.pidx.size();
-    if (hipSetDevice(A->device) != hipSuccess) return finish(CDC_E_DEVICE);
+    if (hipSetDevice(A->src.device) != hipSuccess) return finish(CDC_E_DEVICE);
     if (path) {
         X.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
         if (X.fd < 0) return finish(CDC_E_IO);
@@ -576,9 +481,8 @@ int cdc_archive_new(int device, const cdc_archive_opts *opts, cdc_archive **out)
     auto *a = new (std::nothrow) cdc_archive();
     if (!a) return CDC_E_NOMEM;
     try {
-        a->device = device;
+        a->src.open(device, opts->compress, opts->key);
         a->o = *opts;
-        if (opts->key) a->key.assign(opts->key, opts->key + 32);
         a->o.key = nullptr;
         if (!a->o.writers) a->o.writers = 8;
         if (!a->o.batch_bytes) a->o.batch_bytes = 256ull << 20;
@@ -610,43 +514,24 @@ int cdc_archive_new_zip(int device, const cdc_archive_opts *opts, cdc_archive **
 int cdc_archive_set_level(cdc_archive *a, int level)
 {
     if (!a || (!cdc::level_ok(level))) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(a->run_mu);
+    std::lock_guard<std::mutex> lk(a->src.run_mu);
     a->level = level;
     return CDC_OK;
 }
 
 int cdc_archive_add_packfile(cdc_archive *a, const uint8_t *bytes, uint64_t len)
 {
-    if (!a || (!bytes && len)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(a->run_mu);
-    try {
-        return a->loc.add_memory(bytes, len);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return a && (bytes || !len) ? a->src.add_memory(bytes, len) : CDC_E_INVALID;
 }
 
 int cdc_archive_add_packfile_path(cdc_archive *a, const char *path)
 {
-    if (!a || !path) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(a->run_mu);
-    try {
-        return a->loc.add_path(path);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return a && path ? a->src.add_path(path) : CDC_E_INVALID;
 }
 
 int cdc_archive_add_packfiles(cdc_archive *a, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
 {
-    if (!a || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(a->run_mu, std::try_to_lock);
-    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
-    try {
-        return cdc::add_packfiles(a->loc, a->stored, a->device, a->o.compress, a->key.empty() ? nullptr : a->key.data(), srcs, n, status);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return a ? a->src.add_many(srcs, n, status) : CDC_E_INVALID;
 }
 
 int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, const char *path, cdc_archive_data_fn on_data,
@@ -659,7 +544,7 @@ int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, con
         if (!E.name || (E.type != CDC_ARCHIVE_FILE && E.type != CDC_ARCHIVE_DIR)) return CDC_E_INVALID;
         if (E.type == CDC_ARCHIVE_FILE && E.nchunks && (!E.checksums || !E.lengths)) return CDC_E_INVALID;
     }
-    std::lock_guard<std::mutex> lk(a->run_mu);
+    std::lock_guard<std::mutex> lk(a->src.run_mu);
     try {
         return (a->zip ? run_zip : run)(a, entries, n, path, on_data, on_entry, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -670,12 +555,7 @@ int cdc_archive_run(cdc_archive *a, const cdc_archive_entry *entries, int n, con
 void cdc_archive_free(cdc_archive *a)
 {
     if (!a) return;
-    (void)hipSetDevice(a->device);
-    if (a->stream) {
-        (void)hipStreamSynchronize(a->stream);
-        (void)hipStreamDestroy(a->stream);
-    }
-    if (!a->key.empty()) std::memset(a->key.data(), 0, a->key.size());
+    a->src.release(&a->stream, 1);
     delete a;
 }
 

@@ -7,9 +7,10 @@
 // hasher whose sum must be Object.Checksum.  Here a run is restore's pipeline
 // over batches of file bytes (restore_plan.h) without an output image:
 //
-//   reader   gathers the batch's distinct encoded blobs into a pinned arena
-//            (memcpy or pread, on `threads` threads) and uploads it;
-//   device   (the calling thread) Decode + check over the distinct blobs; the
+//   reader   gathers the batch's distinct encoded blobs and uploads them
+//            (cdc_reader.h: gather, on `threads` threads);
+//   device   (the calling thread) the shared decode step over the distinct
+//            blobs (cdc_reader.h: decode_batch); the
 //            objects the device takes are hashed by k_object_digest where
 //            their blobs lie (check_plan.h: runs and seam copies), the bytes
 //            of the others are gathered by cdc_assemble_device into a staging
@@ -21,54 +22,29 @@
 // uploaded while batch k is on the device and batch k - 1's host-bound
 // objects are hashed.  A file that spans batches keeps one incremental
 // cdc::Sha256 on the host; the device keeps no midstate between batches.
-#include <fcntl.h>
 #include <hip/hip_runtime.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <array>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "cdc_hostmem.h"
-#include "cdc_internal.h"
-#include "cdc_locator.h"
-#include "cdc_stored.h"
+#include "cdc_reader.h"
 #include "check_plan.h"
 #include "restore_plan.h"
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+using cdc::Clock;
+using cdc::parallel_for;
+using cdc::since;
 
 constexpr uint64_t kMaxBatch = 1ull << 30;
-
-template <class F>
-static void parallel_for(int threads, size_t n, F fn)
-{
-    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
-    if (t <= 1) {
-        for (size_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
 
 // cdc_object_digests_device's per-device scratch: the records and runs (pinned
 // and device) and the seam area, kept across calls and grown on demand.
@@ -143,12 +119,7 @@ int cdc::object_digests(int device, const void *d_data, uint64_t len, const uint
 
 namespace {
 
-struct InSlot {   // reader -> device stage
-    cdc::PinBuf h;
-    cdc::DevBuf d;
-    std::vector<uint64_t> eoff, elen;  // the batch's encoded blobs in the arena
-    std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
-};
+using InSlot = cdc::Arena;  // reader -> device stage
 struct OutSlot {  // device stage -> hasher: the staging image of the host's objects and pieces
     cdc::DevBuf d;
     cdc::PinBuf h;
@@ -160,17 +131,13 @@ struct OutSlot {  // device stage -> hasher: the staging image of the host's obj
 }  // namespace
 
 struct cdc_check {
-    int device = 0;
+    cdc::PackSource src;  // device, codec, locator, run lock
     cdc_check_opts o{};
-    std::vector<uint8_t> key;
-    cdc::Locator loc;
     hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stages, download
     InSlot in[2];
     OutSlot out[2];
     cdc::DevBuf plain, dig;
     cdc::PinBuf hdig;
-    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_check_add_packfiles)
-    std::mutex run_mu;
 };
 
 namespace {
@@ -191,10 +158,8 @@ struct Run {
     std::vector<uint64_t> fsize;
     std::vector<std::array<uint8_t, 32>> fsum;
     std::vector<cdc::Sha256> fsha;             // the host's incremental hasher of a file
-    std::mutex mu;
-    std::condition_variable cv;
+    cdc::Handoff hand;  // the stages' hand-offs: counts of batches past each point
     int uploaded = 0, consumed = 0, staged = 0, hashed = 0;
-    int fail = CDC_OK;
     cdc_check_stats st{};
     double gather_s = 0;  // the device stage's share of d2h_s
 
@@ -203,28 +168,6 @@ struct Run {
     {
         int ok = CDC_OK;
         if (fstatus[fi].compare_exchange_strong(ok, status)) fbad[size_t(fi)] = chunk;
-    }
-    bool wait_for(const int &counter, int want)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return counter >= want || fail != CDC_OK; });
-        return fail == CDC_OK;
-    }
-    void advance(int &counter)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            ++counter;
-        }
-        cv.notify_all();
-    }
-    void abort_run(int status)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (fail == CDC_OK) fail = status;
-        }
-        cv.notify_all();
     }
     void report(int fi)
     {
@@ -243,56 +186,18 @@ struct Run {
     }
 };
 
-// ---- reader stage (restore's) ------------------------------------------------------
+// ---- reader stage ----------------------------------------------------------------------
 static void reader_stage(Run &X)
 {
     cdc_check *R = X.R;
-    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(R->src.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
-        const rplan::Batch &B = X.batches[k];
+        if (!X.hand.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
         InSlot &S = R->in[k & 1];
-        const size_t nb = B.blobs.size();
-        auto t0 = Clock::now();
-        S.eoff.assign(nb, 0);
-        S.elen.assign(nb, 0);
-        S.pre.assign(nb, CDC_OK);
-        uint64_t total = 0;
-        std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
-        for (size_t b = 0; b < nb; ++b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            S.eoff[b] = total;
-            S.elen[b] = L.length;
-            total += L.length;
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-        }
-        if (!S.h.reserve(total) || !S.d.reserve(total)) {
-            for (auto &f : fds)
-                if (f.second >= 0) close(f.second);
-            return X.abort_run(CDC_E_NOMEM);
-        }
-        uint8_t *const h = S.h.as<uint8_t>();
-        parallel_for(R->o.threads, nb, [&](size_t b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (P.mem) {
-                std::memcpy(h + S.eoff[b], P.mem + L.offset, L.length);
-                return;
-            }
-            const int fd = fds.find(L.pack)->second;
-            if (fd < 0 || !cdc::pread_all(fd, h + S.eoff[b], L.length, L.offset)) S.pre[b] = CDC_E_IO;
-        });
-        for (auto &f : fds)
-            if (f.second >= 0) close(f.second);
-        X.st.read_s += since(t0);
-        X.st.encoded_bytes += total;
-        t0 = Clock::now();
-        if (total && (hipMemcpyAsync(S.d.data(), h, total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
-                      hipStreamSynchronize(R->stream[0]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
-        X.st.h2d_s += since(t0);
-        X.advance(X.uploaded);
+        S.set_blobs(R->src.loc, X.batches[k].blobs.data(), X.batches[k].blobs.size());
+        const int st = cdc::gather(R->src.loc, S, R->o.threads, R->stream[0], &X.st.read_s, &X.st.h2d_s, &X.st.encoded_bytes);
+        if (st != CDC_OK) return X.hand.abort_run(st);
+        X.hand.advance(X.uploaded);
     }
 }
 
@@ -300,60 +205,28 @@ static void reader_stage(Run &X)
 static void device_stage(Run &X)
 {
     cdc_check *R = X.R;
-    std::vector<uint64_t> oo, pos, so, sl, sd, lens, obj_seg0;
-    std::vector<int32_t> bst;
-    std::vector<uint8_t> want, to_host;
+    std::vector<uint64_t> so, sl, sd, lens, obj_seg0;
+    std::vector<uint8_t> to_host;
+    cdc::Decoded D;
+    const std::vector<int32_t> &bst = D.bst;
+    const std::vector<uint64_t> &pos = D.pos;
+    const cdc::DecodeCtx C{R->src.device, R->src.compress, R->src.key_ptr(), true, R->stream[1]};
+    const cdc::DecodeTally T{&X.st.decoded_bytes, &X.st.decode_s, &X.st.verify_s};
     std::vector<uint32_t> single, dev_piece;
     const double rate = R->o.host_min_len ? 0.0 : cdc::host_sha256_rate();
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.uploaded, k + 1) || !X.wait_for(X.hashed, k - 1)) return;
+        if (!X.hand.wait_for(X.uploaded, k + 1) || !X.hand.wait_for(X.hashed, k - 1)) return;
         const rplan::Batch &B = X.batches[k];
         InSlot &I = R->in[k & 1];
         OutSlot &O = R->out[k & 1];
         const uint32_t nb = uint32_t(B.blobs.size());
-        if (!R->plain.reserve(B.plain_bytes)) return X.abort_run(CDC_E_NOMEM);
+        if (!R->plain.reserve(B.plain_bytes)) return X.hand.abort_run(CDC_E_NOMEM);
         uint8_t *const plain = R->plain.as<uint8_t>();
-        oo.assign(size_t(nb) + 1, 0);
-        bst.assign(std::max<uint32_t>(nb, 1), CDC_OK);
-        want.resize(size_t(nb) * 32 + 1);
-        for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], R->loc.sums[B.blobs[b].id].b, 32);
-        for (uint32_t b = 0; b < nb; ++b)
-            if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
-        const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
-        int st = cdc::decode_checked(R->device, I.d.data(), I.eoff.data(), I.elen.data(), nb, R->o.compress, key,
-                                     want.data(), plain, B.plain_bytes, oo.data(), bst.data(), R->stream[1],
-                                     &X.st.decode_s, &X.st.verify_s);
-        pos.assign(oo.begin(), oo.end() - 1);
-        uint64_t plain_used = oo[nb];
-        if (st == CDC_E_NOSPACE) {
-            // Some blob decodes to more than its recorded Length: restore's slow
-            // path, the batch's blobs one by one, each into the room its Length
-            // gives it.
-            st = CDC_OK;
-            for (uint32_t b = 0; b < nb && st == CDC_OK; ++b) {
-                uint64_t o2[2] = {0, 0};
-                st = cdc::decode_checked(R->device, I.d.data(), &I.eoff[b], &I.elen[b], 1, R->o.compress, key,
-                                         &want[size_t(b) * 32], plain + B.blobs[b].off, B.blobs[b].len, o2, &bst[b],
-                                         R->stream[1], &X.st.decode_s, &X.st.verify_s);
-                if (st == CDC_E_NOSPACE) {
-                    st = CDC_OK;
-                    bst[b] = CDC_E_MISMATCH;
-                    o2[1] = 0;
-                }
-                pos[b] = B.blobs[b].off;
-                if (bst[b] == CDC_OK && o2[1] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-                X.st.decoded_bytes += o2[1];
-            }
-            plain_used = B.plain_bytes;
-        } else if (st == CDC_OK) {
-            for (uint32_t b = 0; b < nb; ++b)
-                if (bst[b] == CDC_OK && oo[b + 1] - oo[b] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-            X.st.decoded_bytes += oo[nb];
-        }
-        if (st != CDC_OK) return X.abort_run(st);
-        for (uint32_t b = 0; b < nb; ++b)
-            if (I.pre[b] != CDC_OK) bst[b] = I.pre[b];
-        X.advance(X.consumed);
+        D.set_blobs(true, R->src.loc, B.blobs.data(), nb);
+        int st = cdc::decode_batch(C, I, plain, B.plain_bytes, D, T);
+        if (st != CDC_OK) return X.hand.abort_run(st);
+        const uint64_t plain_used = D.plain_used;
+        X.hand.advance(X.consumed);
         // objects with a failed blob are settled, not hashed
         for (const rplan::Piece &P : B.pieces)
             for (uint64_t s = P.seg0; s < P.seg0 + P.nchunks; ++s)
@@ -395,16 +268,16 @@ static void device_stage(Run &X)
                 obj_seg0.push_back(so.size());
             }
             const size_t nd = dev_piece.size(), dig_bytes = nd * 32;
-            if (!R->dig.reserve(dig_bytes) || !R->hdig.reserve(dig_bytes)) return X.abort_run(CDC_E_NOMEM);
+            if (!R->dig.reserve(dig_bytes) || !R->hdig.reserve(dig_bytes)) return X.hand.abort_run(CDC_E_NOMEM);
             uint64_t seam = 0;
             if (!cplan::segments_valid(so.data(), sl.data(), so.size(), obj_seg0.data(), nd, plain_used))
-                return X.abort_run(CDC_E_DEVICE);  // the planner's places are inside what Decode wrote
-            st = cdc::object_digests(R->device, plain, plain_used, so.data(), sl.data(), so.size(), obj_seg0.data(),
+                return X.hand.abort_run(CDC_E_DEVICE);  // the planner's places are inside what Decode wrote
+            st = cdc::object_digests(R->src.device, plain, plain_used, so.data(), sl.data(), so.size(), obj_seg0.data(),
                                      uint32_t(nd), R->dig.as<uint8_t>(), R->stream[1], &seam);
-            if (st != CDC_OK) return X.abort_run(st);
+            if (st != CDC_OK) return X.hand.abort_run(st);
             if (hipMemcpyAsync(R->hdig.data(), R->dig.data(), dig_bytes, hipMemcpyDeviceToHost, R->stream[1]) != hipSuccess ||
                 hipStreamSynchronize(R->stream[1]) != hipSuccess)
-                return X.abort_run(CDC_E_DEVICE);
+                return X.hand.abort_run(CDC_E_DEVICE);
             for (size_t j = 0; j < nd; ++j) {
                 const int fi = X.pidx[B.pieces[dev_piece[j]].file];
                 std::memcpy(X.fsum[size_t(fi)].data(), R->hdig.as<uint8_t>() + 32 * j, 32);
@@ -428,16 +301,16 @@ static void device_stage(Run &X)
                     O.bytes += B.segs[s].len;
                 }
             }
-            if (!O.d.reserve(O.bytes) || !O.h.reserve(O.bytes)) return X.abort_run(CDC_E_NOMEM);
+            if (!O.d.reserve(O.bytes) || !O.h.reserve(O.bytes)) return X.hand.abort_run(CDC_E_NOMEM);
             if (O.bytes) {
-                st = cdc_assemble_device(R->device, plain, plain_used, so.data(), sl.data(), sd.data(), so.size(),
+                st = cdc_assemble_device(R->src.device, plain, plain_used, so.data(), sl.data(), sd.data(), so.size(),
                                          O.d.data(), O.bytes, R->stream[1]);
-                if (st != CDC_OK) return X.abort_run(st);
-                if (hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+                if (st != CDC_OK) return X.hand.abort_run(st);
+                if (hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
             }
             X.gather_s += since(t0);
         }
-        X.advance(X.staged);
+        X.hand.advance(X.staged);
     }
 }
 
@@ -445,16 +318,16 @@ static void device_stage(Run &X)
 static void hasher_stage(Run &X)
 {
     cdc_check *R = X.R;
-    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(R->src.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.staged, k + 1)) return;
+        if (!X.hand.wait_for(X.staged, k + 1)) return;
         const rplan::Batch &B = X.batches[k];
         OutSlot &O = R->out[k & 1];
         const uint8_t *const image = O.h.as<uint8_t>();
         auto t0 = Clock::now();
         if (O.bytes && (hipMemcpyAsync(O.h.data(), O.d.data(), O.bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
                         hipStreamSynchronize(R->stream[2]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
+            return X.hand.abort_run(CDC_E_DEVICE);
         X.st.d2h_s += since(t0);
         t0 = Clock::now();
         // a file has one piece per batch at most: the pieces hash side by side
@@ -485,7 +358,7 @@ static void hasher_stage(Run &X)
             }
             X.report(fi);
         }
-        X.advance(X.hashed);
+        X.hand.advance(X.hashed);
     }
 }
 
@@ -517,17 +390,9 @@ static int run_files(cdc_check *R, const cdc_check_file *files, int n, cdc_check
     for (int i = 0; i < n; ++i) {
         X.fstatus[i].store(CDC_OK);
         const cdc_check_file &F = files[i];
-        std::vector<uint32_t> ids(R->o.fast ? 0 : size_t(F.nchunks));
-        for (uint64_t c = 0; c < F.nchunks; ++c) {
-            cdc::Sum s;
-            std::memcpy(s.b, F.checksums + 32 * c, 32);
-            const auto it = R->loc.index.find(s);
-            if (it == R->loc.index.end()) {
-                X.fail_file(i, CDC_E_NOTFOUND, int64_t(c));
-                break;
-            }
-            if (!R->o.fast) ids[size_t(c)] = it->second;
-        }
+        std::vector<uint32_t> ids(size_t(F.nchunks));  // a fast run only asks whether they are there
+        const int64_t miss = cdc::resolve(R->src.loc, F.checksums, F.nchunks, ids.data());
+        if (miss >= 0) X.fail_file(i, CDC_E_NOTFOUND, miss);
         for (uint64_t c = 0; c < F.nchunks; ++c) X.fsize[size_t(i)] += F.lengths[c];
         if (R->o.fast || X.fstatus[i].load() != CDC_OK) {
             X.report(i);
@@ -540,7 +405,7 @@ static int run_files(cdc_check *R, const cdc_check_file *files, int n, cdc_check
         for (size_t p = 0; p < X.pidx.size(); ++p)
             X.pf.push_back(rplan::File{files[X.pidx[p]].nchunks, X.fblob[p].data(), files[X.pidx[p]].lengths});
         rplan::plan(X.pf.data(), X.pf.size(), R->o.batch_bytes, X.batches);
-        std::vector<bool> used(R->loc.locs.size(), false);
+        std::vector<bool> used(R->src.loc.locs.size(), false);
         for (const rplan::Batch &B : X.batches) {
             X.st.bytes += B.out_bytes;
             X.st.segments += B.segs.size();
@@ -556,12 +421,12 @@ static int run_files(cdc_check *R, const cdc_check_file *files, int n, cdc_check
         X.fsha.resize(size_t(n));
     }
     if (!X.batches.empty()) {
-        if (hipSetDevice(R->device) != hipSuccess) return CDC_E_DEVICE;
+        if (hipSetDevice(R->src.device) != hipSuccess) return CDC_E_DEVICE;
         auto guarded = [&X](void (*stage)(Run &)) {
             try {
                 stage(X);
             } catch (...) {
-                X.abort_run(CDC_E_NOMEM);
+                X.hand.abort_run(CDC_E_NOMEM);
             }
         };
         std::thread reader(guarded, reader_stage);
@@ -574,13 +439,13 @@ static int run_files(cdc_check *R, const cdc_check_file *files, int n, cdc_check
     for (int i = 0; i < n; ++i)
         if (!X.reported[size_t(i)]) {
             X.fhashed[size_t(i)] = 0;
-            X.fstatus[i].store(X.fail != CDC_OK ? X.fail : CDC_E_DEVICE);
+            X.fstatus[i].store(X.hand.fail != CDC_OK ? X.hand.fail : CDC_E_DEVICE);
             X.report(i);
         }
     X.st.d2h_s += X.gather_s;
     X.st.wall_s = since(w0);
     write_stats(stats, X.st);
-    return X.fail;
+    return X.hand.fail;
 }
 
 }  // namespace
@@ -622,9 +487,8 @@ int cdc_check_new(int device, const cdc_check_opts *opts, cdc_check **out)
     auto *c = new (std::nothrow) cdc_check();
     if (!c) return CDC_E_NOMEM;
     try {
-        c->device = device;
+        c->src.open(device, opts->compress, opts->key);
         c->o = *opts;
-        if (opts->key) c->key.assign(opts->key, opts->key + 32);
         c->o.key = nullptr;
         if (!c->o.threads) c->o.threads = 8;
         if (!c->o.batch_bytes) c->o.batch_bytes = 256ull << 20;
@@ -646,36 +510,17 @@ int cdc_check_new(int device, const cdc_check_opts *opts, cdc_check **out)
 
 int cdc_check_add_packfile(cdc_check *c, const uint8_t *bytes, uint64_t len)
 {
-    if (!c || (!bytes && len)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->run_mu);
-    try {
-        return c->loc.add_memory(bytes, len);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return c && (bytes || !len) ? c->src.add_memory(bytes, len) : CDC_E_INVALID;
 }
 
 int cdc_check_add_packfile_path(cdc_check *c, const char *path)
 {
-    if (!c || !path) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->run_mu);
-    try {
-        return c->loc.add_path(path);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return c && path ? c->src.add_path(path) : CDC_E_INVALID;
 }
 
 int cdc_check_add_packfiles(cdc_check *c, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
 {
-    if (!c || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(c->run_mu, std::try_to_lock);
-    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
-    try {
-        return cdc::add_packfiles(c->loc, c->stored, c->device, c->o.compress, c->key.empty() ? nullptr : c->key.data(), srcs, n, status);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return c ? c->src.add_many(srcs, n, status) : CDC_E_INVALID;
 }
 
 int cdc_check_files(cdc_check *c, const cdc_check_file *files, int n, cdc_check_file_fn on_file, void *ctx,
@@ -684,7 +529,7 @@ int cdc_check_files(cdc_check *c, const cdc_check_file *files, int n, cdc_check_
     if (!c || n < 0 || (n && !files) || (stats && stats->struct_size < 8)) return CDC_E_INVALID;
     for (int i = 0; i < n; ++i)
         if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->run_mu);
+    std::lock_guard<std::mutex> lk(c->src.run_mu);
     try {
         return run_files(c, files, n, on_file, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -695,13 +540,7 @@ int cdc_check_files(cdc_check *c, const cdc_check_file *files, int n, cdc_check_
 void cdc_check_free(cdc_check *c)
 {
     if (!c) return;
-    if (c->stream[0] || c->stream[1] || c->stream[2]) (void)hipSetDevice(c->device);
-    for (auto &s : c->stream)
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    if (!c->key.empty()) std::memset(c->key.data(), 0, c->key.size());
+    c->src.release(c->stream, 3);
     delete c;  // the slots' buffers go with it, the streams drained above
 }
 

@@ -5,10 +5,9 @@
 // sizes and content types); a caller had to restore the files and search on
 // the host.  Here a run takes a batch of files, and per batch of whole files
 //
-//   read      reader threads gather the distinct encoded blobs into a pinned
-//             arena (restore's plan: a blob many files share is there once),
-//             one upload;
-//   decode    Decode + SHA-256 compare over the distinct blobs (Check's call);
+//   read      the distinct encoded blobs gathered and uploaded (restore's plan:
+//             a blob many files share is there once; cdc_reader.h: gather);
+//   decode    the shared decode step over them (cdc_reader.h: decode_batch);
 //   assemble  the images of the files laid out back to back;
 //   table, scan, compact
 //             cdc_grep_device's stages over the images (cdc::grep_texts), in
@@ -19,66 +18,37 @@
 //
 // The stages of a batch run in sequence on the calling thread, and the files
 // are reported in file order once everything before them is known.
-#include <fcntl.h>
 #include <hip/hip_runtime.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "cdc_hostmem.h"
-#include "cdc_internal.h"
-#include "cdc_locator.h"
-#include "cdc_stored.h"
+#include "cdc_reader.h"
 #include "grep_plan.h"
 #include "restore_plan.h"
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+using cdc::Clock;
+using cdc::since;
 
 constexpr uint64_t kMaxBatch = 1ull << 30;
 constexpr uint64_t kMaxLines = 1ull << 31;
 
-template <class F>
-static void parallel_for(int threads, size_t n, F fn)
-{
-    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
-    if (t <= 1) {
-        for (size_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
-
 }  // namespace
 
 struct cdc_grep {
-    int device = 0;
+    cdc::PackSource src;  // device, codec, locator, run lock
     cdc_grep_opts o{};
-    std::vector<uint8_t> key;
-    cdc::Locator loc;
     hipStream_t stream = nullptr;
-    cdc::PinBuf hin, hhits, hout;
-    cdc::DevBuf din, plain, image, hits, out;
-    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_grep_add_packfiles)
-    std::mutex run_mu;
+    cdc::Arena in;  // the batch's encoded blobs
+    cdc::PinBuf hhits, hout;
+    cdc::DevBuf plain, image, hits, out;
 };
 
 namespace {
@@ -161,83 +131,21 @@ static int run_batch(Run &X, const std::vector<int> &members)
     X.st.decoded_blobs += nb;
     ++X.st.batches;
     // ---- read and upload
-    auto t0 = Clock::now();
-    std::vector<uint64_t> eoff(nb), elen(nb);
-    std::vector<int32_t> pre(nb, CDC_OK);
-    uint64_t total = 0;
-    std::unordered_map<uint32_t, int> fds;
-    for (uint32_t b = 0; b < nb; ++b) {
-        const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-        eoff[b] = total;
-        elen[b] = L.length;
-        total += L.length;
-        const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-        if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-    }
-    const bool in_ok = R->hin.reserve(total) && R->din.reserve(total);
-    if (in_ok) {
-        uint8_t *const h = R->hin.as<uint8_t>();
-        parallel_for(R->o.threads, nb, [&](size_t b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (P.mem) {
-                std::memcpy(h + eoff[b], P.mem + L.offset, L.length);
-                return;
-            }
-            const int fd = fds.find(L.pack)->second;
-            if (fd < 0 || !cdc::pread_all(fd, h + eoff[b], L.length, L.offset)) pre[b] = CDC_E_IO;
-        });
-    }
-    for (auto &f : fds)
-        if (f.second >= 0) close(f.second);
-    if (!in_ok) return CDC_E_NOMEM;
-    X.st.read_s += since(t0);
-    X.st.encoded_bytes += total;
-    t0 = Clock::now();
-    if (total && (hipMemcpyAsync(R->din.data(), R->hin.data(), total, hipMemcpyHostToDevice, st) != hipSuccess ||
-                  hipStreamSynchronize(st) != hipSuccess))
-        return CDC_E_DEVICE;
-    X.st.h2d_s += since(t0);
-    // ---- Decode and compare (Check's device stage)
+    cdc::Arena &I = R->in;
+    I.set_blobs(R->src.loc, B.blobs.data(), nb);
+    int s = cdc::gather(R->src.loc, I, R->o.threads, st, &X.st.read_s, &X.st.h2d_s, &X.st.encoded_bytes);
+    if (s != CDC_OK) return s;
+    // ---- Decode and compare
     if (!R->plain.reserve(B.plain_bytes)) return CDC_E_NOMEM;
     uint8_t *const plain = R->plain.as<uint8_t>();
-    std::vector<uint64_t> oo(size_t(nb) + 1, 0), pos;
-    std::vector<int32_t> bst(std::max<uint32_t>(nb, 1), CDC_OK);
-    std::vector<uint8_t> want(size_t(nb) * 32 + 1);
-    for (uint32_t b = 0; b < nb; ++b) {
-        std::memcpy(&want[size_t(b) * 32], R->loc.sums[B.blobs[b].id].b, 32);
-        if (pre[b] != CDC_OK) elen[b] = 0;  // never read: nothing of it goes through Decode
-    }
-    const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
-    int s = cdc::decode_checked(R->device, R->din.data(), eoff.data(), elen.data(), nb, R->o.compress, key, want.data(), plain,
-                                B.plain_bytes, oo.data(), bst.data(), st, &X.st.decode_s, &X.st.verify_s);
-    pos.assign(oo.begin(), oo.end() - 1);
-    uint64_t plain_used = oo[nb];
-    if (s == CDC_E_NOSPACE) {
-        // some blob decodes to more than its recorded Length: one by one, each into the room its Length gives it
-        s = CDC_OK;
-        for (uint32_t b = 0; b < nb && s == CDC_OK; ++b) {
-            uint64_t o2[2] = {0, 0};
-            s = cdc::decode_checked(R->device, R->din.data(), &eoff[b], &elen[b], 1, R->o.compress, key, &want[size_t(b) * 32],
-                                    plain + B.blobs[b].off, B.blobs[b].len, o2, &bst[b], st, &X.st.decode_s, &X.st.verify_s);
-            if (s == CDC_E_NOSPACE) {
-                s = CDC_OK;
-                bst[b] = CDC_E_MISMATCH;
-                o2[1] = 0;
-            }
-            pos[b] = B.blobs[b].off;
-            if (bst[b] == CDC_OK && o2[1] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-            X.st.decoded_bytes += o2[1];
-        }
-        plain_used = B.plain_bytes;
-    } else if (s == CDC_OK) {
-        for (uint32_t b = 0; b < nb; ++b)
-            if (bst[b] == CDC_OK && oo[b + 1] - oo[b] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-        X.st.decoded_bytes += oo[nb];
-    }
+    cdc::Decoded D;
+    D.set_blobs(true, R->src.loc, B.blobs.data(), nb);
+    s = cdc::decode_batch(cdc::DecodeCtx{R->src.device, R->src.compress, R->src.key_ptr(), true, st}, I, plain, B.plain_bytes, D,
+                          cdc::DecodeTally{&X.st.decoded_bytes, &X.st.decode_s, &X.st.verify_s});
     if (s != CDC_OK) return s;
-    for (uint32_t b = 0; b < nb; ++b)
-        if (pre[b] != CDC_OK) bst[b] = pre[b];
+    const std::vector<int32_t> &bst = D.bst;
+    const std::vector<uint64_t> &pos = D.pos;
+    const uint64_t plain_used = D.plain_used;
     // a failed blob fails its files: the first such chunk
     for (size_t p = 0; p < B.pieces.size(); ++p) {
         const rplan::Piece &P = B.pieces[p];
@@ -248,7 +156,7 @@ static int run_batch(Run &X, const std::vector<int> &members)
             }
     }
     // ---- the images of the files that go on
-    t0 = Clock::now();
+    auto t0 = Clock::now();
     std::vector<int> live;  // position in members
     std::vector<uint64_t> so, sl, sd, toff, tlen;
     for (size_t m = 0; m < members.size(); ++m) {
@@ -271,7 +179,7 @@ static int run_batch(Run &X, const std::vector<int> &members)
     uint8_t *const image = R->image.as<uint8_t>();
     for (size_t k = 0; k < so.size(); ++k)
         if (sl[k] > plain_used || so[k] > plain_used - sl[k]) return CDC_E_DEVICE;  // the plan's places are inside what Decode wrote
-    s = cdc_assemble_device(R->device, plain, plain_used, so.data(), sl.data(), sd.data(), so.size(), image, B.out_bytes, st);
+    s = cdc_assemble_device(R->src.device, plain, plain_used, so.data(), sl.data(), sd.data(), so.size(), image, B.out_bytes, st);
     if (s != CDC_OK) return s;
     if (hipStreamSynchronize(st) != hipSuccess) return CDC_E_DEVICE;
     X.st.assemble_s += since(t0);
@@ -280,7 +188,7 @@ static int run_batch(Run &X, const std::vector<int> &members)
     const uint32_t ntexts = uint32_t(toff.size());
     std::vector<uint64_t> counts(ntexts);
     uint64_t all = 0;
-    s = cdc_line_table_device(R->device, image, B.out_bytes, toff.data(), tlen.data(), ntexts, nullptr, 0, counts.data(), &all, st);
+    s = cdc_line_table_device(R->src.device, image, B.out_bytes, toff.data(), tlen.data(), ntexts, nullptr, 0, counts.data(), &all, st);
     if (s != CDC_OK && s != CDC_E_NOSPACE) return s;
     X.st.table_s += since(t0);
     std::vector<std::vector<int>> groups(1);  // positions in live
@@ -308,7 +216,7 @@ static int run_batch(Run &X, const std::vector<int> &members)
         for (size_t k = 0; k < nf; ++k) go[k] = toff[size_t(G[k])], gl[k] = tlen[size_t(G[k])];
         uint64_t nhits = 0;
         double times[3] = {0, 0, 0};
-        s = cdc::grep_texts(R->device, image, B.out_bytes, go.data(), gl.data(), uint32_t(nf), X.q->patterns, X.q->pattern_len,
+        s = cdc::grep_texts(R->src.device, image, B.out_bytes, go.data(), gl.data(), uint32_t(nf), X.q->patterns, X.q->pattern_len,
                             X.q->npatterns, X.q->flags, limit, hits_room, R, lines.data(), matched.data(), binary.data(), &nhits, st,
                             times);
         if (s != CDC_OK) return s == CDC_E_NOSPACE ? CDC_E_NOMEM : s;
@@ -329,7 +237,7 @@ static int run_batch(Run &X, const std::vector<int> &members)
             recs.reserve(size_t(nhits));
             out_bytes = gplan::emit_records(hh, nhits, max_line, 0, recs);
             if (!R->out.reserve(out_bytes) || !R->hout.reserve(out_bytes)) return CDC_E_NOMEM;
-            s = cdc_diff_emit_device(R->device, image, B.out_bytes, nullptr, 0, recs.data(), recs.size(), R->out.data(), out_bytes, st);
+            s = cdc_diff_emit_device(R->src.device, image, B.out_bytes, nullptr, 0, recs.data(), recs.size(), R->out.data(), out_bytes, st);
             if (s != CDC_OK) return s;
             if (hipStreamSynchronize(st) != hipSuccess) return CDC_E_DEVICE;
             X.st.emit_s += since(t0);
@@ -384,13 +292,13 @@ static int run_files(cdc_grep *R, const cdc_grep_query *q, const cdc_check_file 
     X.ctx = ctx;
     X.fs.resize(size_t(n));
     X.st.files = uint64_t(n);
-    std::vector<bool> used(R->loc.locs.size(), false);
+    std::vector<bool> used(R->src.loc.locs.size(), false);
     std::vector<int> members;
     uint64_t bytes = 0;
     int fail = CDC_OK;
     auto flush = [&] {
         if (members.empty() || fail != CDC_OK) return;
-        if (hipSetDevice(R->device) != hipSuccess) {
+        if (hipSetDevice(R->src.device) != hipSuccess) {
             fail = CDC_E_DEVICE;
             return;
         }
@@ -403,17 +311,9 @@ static int run_files(cdc_grep *R, const cdc_grep_query *q, const cdc_check_file 
         const cdc_check_file &P = files[i];
         FileState &S = X.fs[size_t(i)];
         S.blob.resize(size_t(P.nchunks));
-        for (uint64_t c = 0; c < P.nchunks; ++c) {
-            cdc::Sum sum;
-            std::memcpy(sum.b, P.checksums + 32 * c, 32);
-            const auto it = R->loc.index.find(sum);
-            if (it == R->loc.index.end()) {
-                X.fail(i, CDC_E_NOTFOUND, int64_t(c));
-                break;
-            }
-            S.blob[size_t(c)] = it->second;
-            S.size += P.lengths[c];
-        }
+        const int64_t miss = cdc::resolve(R->src.loc, P.checksums, P.nchunks, S.blob.data());
+        if (miss >= 0) X.fail(i, CDC_E_NOTFOUND, miss);
+        for (uint64_t c = 0; c < (miss < 0 ? P.nchunks : uint64_t(miss)); ++c) S.size += P.lengths[c];
         if (S.status == CDC_OK && S.size > R->o.batch_bytes) X.fail(i, CDC_E_NOSPACE, -1);
         if (S.status != CDC_OK || S.size == 0) {  // an empty file: 0 lines, no hit, no device work
             S.done = true;
@@ -469,9 +369,8 @@ int cdc_grep_new(int device, const cdc_grep_opts *opts, cdc_grep **out)
     auto *c = new (std::nothrow) cdc_grep();
     if (!c) return CDC_E_NOMEM;
     try {
-        c->device = device;
+        c->src.open(device, opts->compress, opts->key);
         c->o = *opts;
-        if (opts->key) c->key.assign(opts->key, opts->key + 32);
         c->o.key = nullptr;
         if (!c->o.threads) c->o.threads = 8;
         if (!c->o.batch_bytes) c->o.batch_bytes = 256ull << 20;
@@ -491,36 +390,17 @@ int cdc_grep_new(int device, const cdc_grep_opts *opts, cdc_grep **out)
 
 int cdc_grep_add_packfile(cdc_grep *g, const uint8_t *bytes, uint64_t len)
 {
-    if (!g || (!bytes && len)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(g->run_mu);
-    try {
-        return g->loc.add_memory(bytes, len);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return g && (bytes || !len) ? g->src.add_memory(bytes, len) : CDC_E_INVALID;
 }
 
 int cdc_grep_add_packfile_path(cdc_grep *g, const char *path)
 {
-    if (!g || !path) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(g->run_mu);
-    try {
-        return g->loc.add_path(path);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return g && path ? g->src.add_path(path) : CDC_E_INVALID;
 }
 
 int cdc_grep_add_packfiles(cdc_grep *g, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
 {
-    if (!g || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(g->run_mu, std::try_to_lock);
-    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
-    try {
-        return cdc::add_packfiles(g->loc, g->stored, g->device, g->o.compress, g->key.empty() ? nullptr : g->key.data(), srcs, n, status);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return g ? g->src.add_many(srcs, n, status) : CDC_E_INVALID;
 }
 
 int cdc_grep_files(cdc_grep *g, const cdc_grep_query *q, const cdc_check_file *files, int n, cdc_grep_file_fn on_file, void *ctx,
@@ -531,7 +411,7 @@ int cdc_grep_files(cdc_grep *g, const cdc_grep_query *q, const cdc_check_file *f
         return CDC_E_INVALID;
     for (int i = 0; i < n; ++i)
         if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(g->run_mu);
+    std::lock_guard<std::mutex> lk(g->src.run_mu);
     try {
         return run_files(g, q, files, n, on_file, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -542,12 +422,7 @@ int cdc_grep_files(cdc_grep *g, const cdc_grep_query *q, const cdc_check_file *f
 void cdc_grep_free(cdc_grep *g)
 {
     if (!g) return;
-    if (g->stream) {
-        (void)hipSetDevice(g->device);
-        (void)hipStreamSynchronize(g->stream);
-        (void)hipStreamDestroy(g->stream);
-    }
-    if (!g->key.empty()) std::memset(g->key.data(), 0, g->key.size());
+    g->src.release(&g->stream, 1);
     delete g;
 }
 

@@ -36,13 +36,13 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "cdc_hostmem.h"
+#include "cdc_hostutil.h"
 #include "cdc_internal.h"
 #include "grep_plan.h"
 
@@ -322,8 +322,8 @@ __global__ __launch_bounds__(kThreads) void k_grep_compact(const Text *texts, ui
 }
 
 // ---- host side ------------------------------------------------------------------------
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+using cdc::Clock;
+using cdc::since;
 
 struct Scratch {  // per device, kept across calls and grown on demand
     std::mutex mu;

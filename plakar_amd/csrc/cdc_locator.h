@@ -10,12 +10,12 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <cerrno>
 #include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "cdc_hostutil.h"
 #include "cdc_internal.h"
 #include "restore_plan.h"
 
@@ -33,31 +33,6 @@ struct SumHash {  // the checksums are SHA-256: any eight bytes are a hash
         return size_t(v);
     }
 };
-
-inline bool pread_all(int fd, uint8_t *dst, uint64_t len, uint64_t off)
-{
-    while (len) {
-        const ssize_t r = pread(fd, dst, len, off_t(off));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        dst += r;
-        off += uint64_t(r);
-        len -= uint64_t(r);
-    }
-    return true;
-}
-
-inline bool write_all(int fd, const uint8_t *src, uint64_t len)
-{
-    while (len) {
-        const ssize_t r = write(fd, src, len);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        src += r;
-        len -= uint64_t(r);
-    }
-    return true;
-}
 
 struct Locator {
     struct Pack {

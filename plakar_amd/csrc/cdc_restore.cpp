@@ -8,9 +8,10 @@
 // is verified.  Here a run is a pipeline over batches of output bytes planned
 // up front (restore_plan.h), three stages on three threads and three streams:
 //
-//   reader   gathers the batch's distinct encoded blobs into a pinned arena
-//            (memcpy or pread, on `writers` threads) and uploads it;
-//   device   (the calling thread) Decode + check over the distinct blobs, then
+//   reader   gathers the batch's distinct encoded blobs and uploads them
+//            (cdc_reader.h: gather, on `writers` threads);
+//   device   (the calling thread) the shared decode step over the distinct
+//            blobs (cdc_reader.h: decode_together, decode_one_by_one), then
 //            cdc_assemble_device into the batch's output image, or nothing
 //            when the plaintext buffer already is that image;
 //   writer   downloads the image into a pinned slot, pwrites every piece
@@ -27,69 +28,25 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cerrno>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "cdc_hostmem.h"
-#include "cdc_internal.h"
-#include "cdc_locator.h"
-#include "cdc_stored.h"
+#include "cdc_reader.h"
 #include "read_plan.h"
 #include "restore_plan.h"
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+using cdc::Clock;
+using cdc::parallel_for;
+using cdc::pwrite_all;
+using cdc::since;
+using InSlot = cdc::Arena;  // reader -> device stage
 
-using cdc::pread_all;
-
-static bool pwrite_all(int fd, const uint8_t *src, uint64_t len, uint64_t off)
-{
-    while (len) {
-        const ssize_t r = pwrite(fd, src, len, off_t(off));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        src += r;
-        off += uint64_t(r);
-        len -= uint64_t(r);
-    }
-    return true;
-}
-
-template <class F>
-static void parallel_for(int threads, size_t n, F fn)
-{
-    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
-    if (t <= 1) {
-        for (size_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
-
-struct InSlot {   // reader -> device stage
-    cdc::PinBuf h;
-    cdc::DevBuf d;
-    std::vector<uint64_t> eoff, elen;  // the batch's encoded blobs in the arena
-    std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
-};
 struct OutSlot {  // device stage -> writer
     cdc::DevBuf d;
     cdc::PinBuf h;
@@ -98,16 +55,12 @@ struct OutSlot {  // device stage -> writer
 }  // namespace
 
 struct cdc_restore {
-    int device = 0;
+    cdc::PackSource src;  // device, codec, locator, run lock
     cdc_restore_opts o{};
-    std::vector<uint8_t> key;
-    cdc::Locator loc;  // the registered packfiles: checksum -> blob id -> (packfile, offset, length)
     hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stages, download
     InSlot in[2];
     OutSlot out[2];
     cdc::DevBuf plain;
-    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_restore_add_packfiles)
-    std::mutex run_mu;
 };
 
 namespace {
@@ -127,10 +80,8 @@ struct Run {
     std::vector<uint64_t> fsize;
     std::vector<uint32_t> fpieces, fseen;
     // the stages' hand-offs: counts of batches past each point
-    std::mutex mu;
-    std::condition_variable cv;
+    cdc::Handoff hand;
     int uploaded = 0, consumed = 0, assembled = 0, written = 0;
-    int fail = CDC_OK;
     cdc_restore_stats st{};
     double read_s = 0, h2d_s = 0, decode_s = 0, verify_s = 0, assemble_s = 0, d2h_s = 0, write_s = 0;
 
@@ -138,29 +89,6 @@ struct Run {
     {
         int ok = CDC_OK;
         fstatus[fi].compare_exchange_strong(ok, status);
-    }
-    // Wait until `counter` reaches `want`; false when the run has failed.
-    bool wait_for(const int &counter, int want)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return counter >= want || fail != CDC_OK; });
-        return fail == CDC_OK;
-    }
-    void advance(int &counter)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            ++counter;
-        }
-        cv.notify_all();
-    }
-    void abort_run(int status)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (fail == CDC_OK) fail = status;
-        }
-        cv.notify_all();
     }
     void report(int fi, int status, uint32_t piece, uint32_t pieces, const uint8_t *data, uint64_t off, uint64_t len)
     {
@@ -182,52 +110,14 @@ struct Run {
 static void reader_stage(Run &X)
 {
     cdc_restore *R = X.R;
-    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(R->src.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
-        const rplan::Batch &B = X.batches[k];
+        if (!X.hand.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
         InSlot &S = R->in[k & 1];
-        const size_t nb = B.blobs.size();
-        auto t0 = Clock::now();
-        S.eoff.assign(nb, 0);
-        S.elen.assign(nb, 0);
-        S.pre.assign(nb, CDC_OK);
-        uint64_t total = 0;
-        std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
-        for (size_t b = 0; b < nb; ++b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            S.eoff[b] = total;
-            S.elen[b] = L.length;
-            total += L.length;
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-        }
-        if (!S.h.reserve(total) || !S.d.reserve(total)) {
-            for (auto &f : fds)
-                if (f.second >= 0) close(f.second);
-            return X.abort_run(CDC_E_NOMEM);
-        }
-        uint8_t *const h = S.h.as<uint8_t>();
-        parallel_for(R->o.writers, nb, [&](size_t b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (P.mem) {
-                std::memcpy(h + S.eoff[b], P.mem + L.offset, L.length);
-                return;
-            }
-            const int fd = fds.find(L.pack)->second;
-            if (fd < 0 || !pread_all(fd, h + S.eoff[b], L.length, L.offset)) S.pre[b] = CDC_E_IO;
-        });
-        for (auto &f : fds)
-            if (f.second >= 0) close(f.second);
-        X.read_s += since(t0);
-        X.st.encoded_bytes += total;
-        t0 = Clock::now();
-        if (total && (hipMemcpyAsync(S.d.data(), h, total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
-                      hipStreamSynchronize(R->stream[0]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
-        X.h2d_s += since(t0);
-        X.advance(X.uploaded);
+        S.set_blobs(R->src.loc, X.batches[k].blobs.data(), X.batches[k].blobs.size());
+        const int st = cdc::gather(R->src.loc, S, R->o.writers, R->stream[0], &X.read_s, &X.h2d_s, &X.st.encoded_bytes);
+        if (st != CDC_OK) return X.hand.abort_run(st);
+        X.hand.advance(X.uploaded);
     }
 }
 
@@ -235,70 +125,31 @@ static void reader_stage(Run &X)
 static void device_stage(Run &X)
 {
     cdc_restore *R = X.R;
-    std::vector<uint64_t> oo, pos, so, sl, sd;
-    std::vector<int32_t> bst;
-    std::vector<uint8_t> want;
+    std::vector<uint64_t> so, sl, sd;
+    cdc::Decoded D;
+    const std::vector<int32_t> &bst = D.bst;
+    const cdc::DecodeCtx C{R->src.device, R->src.compress, R->src.key_ptr(), R->o.verify != 0, R->stream[1]};
+    const cdc::DecodeTally T{&X.st.decoded_bytes, &X.decode_s, &X.verify_s};
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.uploaded, k + 1) || !X.wait_for(X.written, k - 1)) return;
+        if (!X.hand.wait_for(X.uploaded, k + 1) || !X.hand.wait_for(X.written, k - 1)) return;
         const rplan::Batch &B = X.batches[k];
         InSlot &I = R->in[k & 1];
         OutSlot &O = R->out[k & 1];
         const uint32_t nb = uint32_t(B.blobs.size());
         bool direct = B.identity;  // decode straight into the output image
         if (!O.d.reserve(B.out_bytes) || !O.h.reserve(B.out_bytes) || (!direct && !R->plain.reserve(B.plain_bytes)))
-            return X.abort_run(CDC_E_NOMEM);
+            return X.hand.abort_run(CDC_E_NOMEM);
         uint8_t *const out = O.d.as<uint8_t>();
-        int st;
-        oo.assign(size_t(nb) + 1, 0);
-        bst.assign(std::max<uint32_t>(nb, 1), CDC_OK);
-        if (R->o.verify) {
-            want.resize(size_t(nb) * 32 + 1);
-            for (uint32_t b = 0; b < nb; ++b) std::memcpy(&want[size_t(b) * 32], R->loc.sums[B.blobs[b].id].b, 32);
-        }
-        for (uint32_t b = 0; b < nb; ++b)
-            if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
-        const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
-        const uint8_t *sums = R->o.verify ? want.data() : nullptr;
-        st = cdc::decode_checked(R->device, I.d.data(), I.eoff.data(), I.elen.data(), nb, R->o.compress, key, sums,
-                                 direct ? out : R->plain.as<uint8_t>(), B.plain_bytes, oo.data(), bst.data(), R->stream[1],
-                                 &X.decode_s, &X.verify_s);
-        pos.assign(oo.begin(), oo.end() - 1);
-        uint64_t plain_used = oo[nb];
-        if (st == CDC_E_NOSPACE) {
-            // Some blob decodes to more than its recorded Length, by an amount
-            // only its own bytes bound.  Decode the batch's blobs one by one,
-            // each into the room its Length gives it: the ones that fit come
-            // out, the others are the mismatch.  (A slow path: it runs only
-            // for a batch that holds such a blob.)
+        D.set_blobs(C.verify, R->src.loc, B.blobs.data(), nb);
+        int st = cdc::decode_together(C, I, direct ? out : R->plain.as<uint8_t>(), B.plain_bytes, D, T);
+        if (st == CDC_E_NOSPACE) {  // the slow path: never into the output image
             direct = false;
-            st = R->plain.reserve(B.plain_bytes) ? CDC_OK : CDC_E_NOMEM;
-            for (uint32_t b = 0; b < nb && st == CDC_OK; ++b) {
-                uint64_t o2[2] = {0, 0};
-                st = cdc::decode_checked(R->device, I.d.data(), &I.eoff[b], &I.elen[b], 1, R->o.compress, key,
-                                         sums ? sums + size_t(b) * 32 : nullptr, R->plain.as<uint8_t>() + B.blobs[b].off,
-                                         B.blobs[b].len, o2, &bst[b], R->stream[1], &X.decode_s, &X.verify_s);
-                if (st == CDC_E_NOSPACE) {
-                    st = CDC_OK;
-                    bst[b] = CDC_E_MISMATCH;
-                    o2[1] = 0;
-                }
-                pos[b] = B.blobs[b].off;
-                if (bst[b] == CDC_OK && o2[1] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-                X.st.decoded_bytes += o2[1];
-            }
-            plain_used = B.plain_bytes;
-        } else if (st == CDC_OK) {
-            for (uint32_t b = 0; b < nb; ++b)
-                if (bst[b] == CDC_OK && oo[b + 1] - oo[b] != B.blobs[b].len) bst[b] = CDC_E_MISMATCH;
-            X.st.decoded_bytes += oo[nb];
+            st = R->plain.reserve(B.plain_bytes) ? cdc::decode_one_by_one(C, I, R->plain.as<uint8_t>(), B.plain_bytes, D, T)
+                                                 : CDC_E_NOMEM;
         }
-        if (st != CDC_OK) return X.abort_run(st);
-        bool bad = false;
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (I.pre[b] != CDC_OK) bst[b] = I.pre[b];
-            bad = bad || bst[b] != CDC_OK;
-        }
-        X.advance(X.consumed);
+        if (st != CDC_OK) return X.hand.abort_run(st);
+        const bool bad = std::any_of(bst.begin(), bst.begin() + nb, [](int32_t s) { return s != CDC_OK; });
+        X.hand.advance(X.consumed);
         if (bad)
             for (const rplan::Piece &P : B.pieces)
                 for (uint64_t s = P.seg0; s < P.seg0 + P.nchunks; ++s)
@@ -312,27 +163,27 @@ static void device_stage(Run &X)
             const auto t0 = Clock::now();
             bool ok = true;
             if (direct) {  // the plaintext sits compacted in the image: move it out of the way first
-                if (!R->plain.reserve(plain_used)) return X.abort_run(CDC_E_NOMEM);
-                ok = !plain_used ||
-                     hipMemcpyAsync(R->plain.data(), out, plain_used, hipMemcpyDeviceToDevice, R->stream[1]) == hipSuccess;
+                if (!R->plain.reserve(D.plain_used)) return X.hand.abort_run(CDC_E_NOMEM);
+                ok = !D.plain_used ||
+                     hipMemcpyAsync(R->plain.data(), out, D.plain_used, hipMemcpyDeviceToDevice, R->stream[1]) == hipSuccess;
             }
             so.clear();
             sl.clear();
             sd.clear();
             for (const rplan::Segment &S : B.segs) {
                 if (bst[S.blob] != CDC_OK) continue;  // its files have failed; their bytes are not delivered
-                so.push_back(pos[S.blob]);
+                so.push_back(D.pos[S.blob]);
                 sl.push_back(S.len);
                 sd.push_back(S.dst_off);
             }
             if (ok && !so.empty())
-                st = cdc_assemble_device(R->device, R->plain.data(), plain_used, so.data(), sl.data(), sd.data(), so.size(), out,
+                st = cdc_assemble_device(R->src.device, R->plain.data(), D.plain_used, so.data(), sl.data(), sd.data(), so.size(), out,
                                          B.out_bytes, R->stream[1]);
-            if (st != CDC_OK) return X.abort_run(st);
-            if (!ok || hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+            if (st != CDC_OK) return X.hand.abort_run(st);
+            if (!ok || hipStreamSynchronize(R->stream[1]) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
             X.assemble_s += since(t0);
         }
-        X.advance(X.assembled);
+        X.hand.advance(X.assembled);
     }
 }
 
@@ -352,16 +203,16 @@ static void write_piece(Run &X, const rplan::Piece &P, const uint8_t *image)
 static void writer_stage(Run &X)
 {
     cdc_restore *R = X.R;
-    if (hipSetDevice(R->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(R->src.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     for (int k = 0; k < int(X.batches.size()); ++k) {
-        if (!X.wait_for(X.assembled, k + 1)) return;
+        if (!X.hand.wait_for(X.assembled, k + 1)) return;
         const rplan::Batch &B = X.batches[k];
         OutSlot &O = R->out[k & 1];
         uint8_t *const image = O.h.as<uint8_t>();
         auto t0 = Clock::now();
         if (B.out_bytes && (hipMemcpyAsync(image, O.d.data(), B.out_bytes, hipMemcpyDeviceToHost, R->stream[2]) != hipSuccess ||
                             hipStreamSynchronize(R->stream[2]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
+            return X.hand.abort_run(CDC_E_DEVICE);
         X.d2h_s += since(t0);
         t0 = Clock::now();
         parallel_for(R->o.writers, B.pieces.size(), [&](size_t i) { write_piece(X, B.pieces[i], image); });
@@ -385,7 +236,7 @@ static void writer_stage(Run &X)
                          s == CDC_OK ? P.len : 0);
             }
         }
-        X.advance(X.written);
+        X.hand.advance(X.written);
     }
 }
 
@@ -410,16 +261,11 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
         X.fstatus[i].store(CDC_OK);
         const cdc_restore_file &F = files[i];
         std::vector<uint32_t> ids(size_t(F.nchunks));
-        for (uint64_t c = 0; c < F.nchunks; ++c) {
-            cdc::Sum s;
-            std::memcpy(s.b, F.checksums + 32 * c, 32);
-            const auto it = R->loc.index.find(s);
-            if (it == R->loc.index.end()) {
-                X.fstatus[i].store(CDC_E_NOTFOUND);
-                break;
-            }
-            ids[size_t(c)] = it->second;
-            X.fsize[i] += F.lengths[c];
+        const int64_t miss = cdc::resolve(R->src.loc, F.checksums, F.nchunks, ids.data());
+        for (uint64_t c = 0; c < (miss < 0 ? F.nchunks : uint64_t(miss)); ++c) X.fsize[i] += F.lengths[c];
+        if (miss >= 0) {
+            X.fstatus[i].store(CDC_E_NOTFOUND);
+            continue;
         }
         if (X.fstatus[i].load() != CDC_OK) continue;
         X.fblob.push_back(std::move(ids));
@@ -428,7 +274,7 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     for (size_t p = 0; p < X.pidx.size(); ++p)
         X.pf.push_back(rplan::File{files[X.pidx[p]].nchunks, X.fblob[p].data(), files[X.pidx[p]].lengths});
     rplan::plan(X.pf.data(), X.pf.size(), R->o.batch_bytes, X.batches);
-    std::vector<bool> used(R->loc.locs.size(), false);
+    std::vector<bool> used(R->src.loc.locs.size(), false);
     for (const rplan::Batch &B : X.batches) {
         X.st.bytes += B.out_bytes;
         X.st.segments += B.segs.size();
@@ -449,12 +295,12 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
             X.report(i, X.fstatus[i].load(), 0, 1, nullptr, 0, 0);
         }
     if (!X.batches.empty()) {
-        if (hipSetDevice(R->device) != hipSuccess) return CDC_E_DEVICE;
+        if (hipSetDevice(R->src.device) != hipSuccess) return CDC_E_DEVICE;
         auto guarded = [&X](void (*stage)(Run &)) {
             try {
                 stage(X);
             } catch (...) {
-                X.abort_run(CDC_E_NOMEM);
+                X.hand.abort_run(CDC_E_NOMEM);
             }
         };
         std::thread reader(guarded, reader_stage);
@@ -467,7 +313,7 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     for (int i = 0; i < n; ++i) {
         if (!X.reported[i]) {
             if (files[i].path && X.created[i]) unlink(files[i].path);
-            X.fstatus[i].store(X.fail != CDC_OK ? X.fail : CDC_E_DEVICE);
+            X.fstatus[i].store(X.hand.fail != CDC_OK ? X.hand.fail : CDC_E_DEVICE);
             X.report(i, X.fstatus[i].load(), 0, 1, nullptr, 0, 0);
         }
         X.st.failed_files += X.fstatus[i].load() != CDC_OK;
@@ -481,7 +327,7 @@ static int run_files(cdc_restore *R, const cdc_restore_file *files, int n, cdc_r
     X.st.write_s = X.write_s;
     X.st.wall_s = since(w0);
     if (stats) *stats = X.st;
-    return X.fail;
+    return X.hand.fail;
 }
 
 // ---- ranged reads -------------------------------------------------------------------
@@ -501,13 +347,14 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
     for (int i = 0; i < nfiles; ++i) {
         const cdc_restore_file &F = files[i];
         fblob[size_t(i)].resize(size_t(F.nchunks));
-        for (uint64_t c = 0; c < F.nchunks; ++c) {
-            cdc::Sum s;
-            std::memcpy(s.b, F.checksums + 32 * c, 32);
-            const auto it = R->loc.index.find(s);
-            fblob[size_t(i)][size_t(c)] = it == R->loc.index.end() ? rplan::kMissing : it->second;
+        uint32_t *const ids = fblob[size_t(i)].data();
+        for (uint64_t c = 0; c < F.nchunks; ++c) {  // past every miss
+            const int64_t miss = cdc::resolve(R->src.loc, F.checksums + 32 * c, F.nchunks - c, ids + c);
+            if (miss < 0) break;
+            c += uint64_t(miss);
+            ids[c] = rplan::kMissing;
         }
-        pf.push_back(rplan::File{F.nchunks, fblob[size_t(i)].data(), F.lengths});
+        pf.push_back(rplan::File{F.nchunks, ids, F.lengths});
     }
     std::vector<rplan::Range> rr;
     for (int i = 0; i < nranges; ++i) rr.push_back(rplan::Range{ranges[i].file, ranges[i].offset, ranges[i].length});
@@ -533,7 +380,7 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
         rstatus[size_t(i)] = info[size_t(i)].status;
         if (rstatus[size_t(i)] != CDC_OK) report(i, 0, nullptr, 0, 0);
     }
-    std::vector<bool> used(R->loc.locs.size(), false);
+    std::vector<bool> used(R->src.loc.locs.size(), false);
     for (const rplan::RBatch &B : batches) {
         st.bytes += B.out_bytes;
         st.segments += B.segs.size();
@@ -549,8 +396,8 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
     }
     st.batches = batches.size();
     int fail = CDC_OK;
-    if (!batches.empty() && hipSetDevice(R->device) != hipSuccess) fail = CDC_E_DEVICE;
-    const uint8_t *key = R->key.empty() ? nullptr : R->key.data();
+    if (!batches.empty() && hipSetDevice(R->src.device) != hipSuccess) fail = CDC_E_DEVICE;
+    const uint8_t *key = R->src.key_ptr();
     InSlot &I = R->in[0];
     OutSlot &O = R->out[0];
     std::vector<uint64_t> upto, oo, so, sl, sd;
@@ -561,53 +408,13 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
         const rplan::RBatch &B = batches[done];
         const size_t nb = B.blobs.size();
         // gather: whole blobs, or without compression the header and the records that hold the prefix
-        auto t0 = Clock::now();
-        I.eoff.assign(nb, 0);
-        I.elen.assign(nb, 0);
-        I.pre.assign(nb, CDC_OK);
-        uint64_t total = 0;
-        std::unordered_map<uint32_t, int> fds;
-        for (size_t b = 0; b < nb; ++b) {
-            const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-            uint64_t need = L.length;
-            if (R->o.compress == CDC_COMPRESS_NONE)
-                need = std::min<uint64_t>(need, key ? kGcmHeader + (B.blobs[b].upto + 65535) / 65536 * kGcmRecord
-                                                    : B.blobs[b].upto);
-            I.eoff[b] = total;
-            I.elen[b] = need;
-            total += need;
-            const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-            if (!P.mem && !fds.count(L.pack)) fds[L.pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-        }
-        const bool room = I.h.reserve(total) && I.d.reserve(total);
-        if (room) {
-            uint8_t *const h = I.h.as<uint8_t>();
-            parallel_for(R->o.writers, nb, [&](size_t b) {
-                const cdc::Locator::Loc &L = R->loc.locs[B.blobs[b].id];
-                const cdc::Locator::Pack &P = R->loc.packs[L.pack];
-                if (P.mem) {
-                    std::memcpy(h + I.eoff[b], P.mem + L.offset, I.elen[b]);
-                    return;
-                }
-                const int fd = fds.find(L.pack)->second;
-                if (fd < 0 || !pread_all(fd, h + I.eoff[b], I.elen[b], L.offset)) I.pre[b] = CDC_E_IO;
-            });
-        }
-        for (auto &f : fds)
-            if (f.second >= 0) close(f.second);
-        if (!room) {
-            fail = CDC_E_NOMEM;
-            break;
-        }
-        st.read_s += since(t0);
-        st.encoded_bytes += total;
-        t0 = Clock::now();
-        if (total && (hipMemcpyAsync(I.d.data(), I.h.data(), total, hipMemcpyHostToDevice, R->stream[0]) != hipSuccess ||
-                      hipStreamSynchronize(R->stream[0]) != hipSuccess)) {
-            fail = CDC_E_DEVICE;
-            break;
-        }
-        st.h2d_s += since(t0);
+        I.set_blobs(R->src.loc, B.blobs.data(), nb);
+        if (R->src.compress == CDC_COMPRESS_NONE)
+            for (size_t b = 0; b < nb; ++b)
+                I.spans[b].length = std::min<uint64_t>(
+                    I.spans[b].length, key ? kGcmHeader + (B.blobs[b].upto + 65535) / 65536 * kGcmRecord : B.blobs[b].upto);
+        fail = cdc::gather(R->src.loc, I, R->o.writers, R->stream[0], &st.read_s, &st.h2d_s, &st.encoded_bytes);
+        if (fail != CDC_OK) break;
         // prefix Decode into the scratch buffer, the check of the blobs decoded whole
         if (!R->plain.reserve(B.scratch_bytes) || !O.d.reserve(B.out_bytes) || !O.h.reserve(B.out_bytes)) {
             fail = CDC_E_NOMEM;
@@ -621,11 +428,11 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
         for (size_t b = 0; b < nb; ++b) {
             upto[b] = B.blobs[b].upto;
             whole[b] = B.blobs[b].upto == B.blobs[b].len;
-            std::memcpy(&want[b * 32], R->loc.sums[B.blobs[b].id].b, 32);
+            std::memcpy(&want[b * 32], R->src.loc.sums[B.blobs[b].id].b, 32);
             if (I.pre[b] != CDC_OK) I.elen[b] = 0;  // never read: nothing of it goes through Decode
         }
-        int rc = cdc::decode_prefix_checked(R->device, I.d.data(), I.eoff.data(), I.elen.data(), upto.data(), uint32_t(nb),
-                                            R->o.compress, key, R->o.verify ? want.data() : nullptr, whole.data(),
+        int rc = cdc::decode_prefix_checked(R->src.device, I.d.data(), I.eoff.data(), I.elen.data(), upto.data(), uint32_t(nb),
+                                            R->src.compress, key, R->o.verify ? want.data() : nullptr, whole.data(),
                                             R->plain.as<uint8_t>(), B.scratch_bytes, oo.data(), bst.data(), R->stream[1],
                                             &st.decode_s, &st.verify_s);
         if (rc != CDC_OK) {
@@ -642,7 +449,7 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
                 const int32_t e = bst[B.segs[size_t(s)].blob];
                 if (e != CDC_OK && rstatus[P.range] == CDC_OK) rstatus[P.range] = e;
             }
-        t0 = Clock::now();
+        auto t0 = Clock::now();
         so.clear();
         sl.clear();
         sd.clear();
@@ -653,7 +460,7 @@ static int run_ranges(cdc_restore *R, const cdc_restore_file *files, int nfiles,
             sd.push_back(S.dst_off);
         }
         if (!so.empty())
-            rc = cdc_assemble_device(R->device, R->plain.data(), B.scratch_bytes, so.data(), sl.data(), sd.data(), so.size(),
+            rc = cdc_assemble_device(R->src.device, R->plain.data(), B.scratch_bytes, so.data(), sl.data(), sd.data(), so.size(),
                                      O.d.data(), B.out_bytes, R->stream[1]);
         if (rc == CDC_OK && hipStreamSynchronize(R->stream[1]) != hipSuccess) rc = CDC_E_DEVICE;
         if (rc != CDC_OK) {
@@ -717,9 +524,8 @@ int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out)
     auto *r = new (std::nothrow) cdc_restore();
     if (!r) return CDC_E_NOMEM;
     try {
-        r->device = device;
+        r->src.open(device, opts->compress, opts->key);
         r->o = *opts;
-        if (opts->key) r->key.assign(opts->key, opts->key + 32);
         r->o.key = nullptr;
         if (!r->o.writers) r->o.writers = 8;
         if (!r->o.batch_bytes) r->o.batch_bytes = 256ull << 20;
@@ -739,36 +545,17 @@ int cdc_restore_new(int device, const cdc_restore_opts *opts, cdc_restore **out)
 
 int cdc_restore_add_packfile(cdc_restore *r, const uint8_t *bytes, uint64_t len)
 {
-    if (!r || (!bytes && len)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(r->run_mu);
-    try {
-        return r->loc.add_memory(bytes, len);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return r && (bytes || !len) ? r->src.add_memory(bytes, len) : CDC_E_INVALID;
 }
 
 int cdc_restore_add_packfile_path(cdc_restore *r, const char *path)
 {
-    if (!r || !path) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(r->run_mu);
-    try {
-        return r->loc.add_path(path);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return r && path ? r->src.add_path(path) : CDC_E_INVALID;
 }
 
 int cdc_restore_add_packfiles(cdc_restore *r, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
 {
-    if (!r || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(r->run_mu, std::try_to_lock);
-    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
-    try {
-        return cdc::add_packfiles(r->loc, r->stored, r->device, r->o.compress, r->key.empty() ? nullptr : r->key.data(), srcs, n, status);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return r ? r->src.add_many(srcs, n, status) : CDC_E_INVALID;
 }
 
 int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_restore_file_fn on_file, void *ctx,
@@ -777,7 +564,7 @@ int cdc_restore_files(cdc_restore *r, const cdc_restore_file *files, int n, cdc_
     if (!r || n < 0 || (n && !files)) return CDC_E_INVALID;
     for (int i = 0; i < n; ++i)
         if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(r->run_mu);
+    std::lock_guard<std::mutex> lk(r->src.run_mu);
     try {
         return run_files(r, files, n, on_file, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -792,7 +579,7 @@ int cdc_restore_ranges(cdc_restore *r, const cdc_restore_file *files, int nfiles
         return CDC_E_INVALID;
     for (int i = 0; i < nfiles; ++i)
         if (files[i].nchunks && (!files[i].checksums || !files[i].lengths)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(r->run_mu);
+    std::lock_guard<std::mutex> lk(r->src.run_mu);
     try {
         return run_ranges(r, files, nfiles, ranges, nranges, on_range, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -803,13 +590,7 @@ int cdc_restore_ranges(cdc_restore *r, const cdc_restore_file *files, int nfiles
 void cdc_restore_free(cdc_restore *r)
 {
     if (!r) return;
-    (void)hipSetDevice(r->device);
-    for (auto &s : r->stream)
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    if (!r->key.empty()) std::memset(r->key.data(), 0, r->key.size());
+    r->src.release(r->stream, 3);
     delete r;  // the slots' buffers and `plain` go with it, the streams drained above
 }
 

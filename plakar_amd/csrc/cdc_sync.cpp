@@ -9,8 +9,8 @@
 // a run is a pipeline over batches of stored blobs planned up front
 // (sync_plan.h), three stages on three threads and three streams:
 //
-//   reader   gathers the batch's stored blobs into a pinned arena (memcpy or
-//            pread, on `readers` threads) and uploads it;
+//   reader   gathers the batch's stored blobs and uploads them (cdc_reader.h:
+//            gather, on `readers` threads);
 //   device   (the calling thread) one cdc_transcode_device_level call over the
 //            blobs that were read: the check when verify is set, then the
 //            re-key, open, seal, copy or re-encode;
@@ -23,52 +23,27 @@
 // uploaded while batch k is on the device and batch k - 1 is downloaded and
 // packed.  Transcode is synchronous and holds the per-device workspace, so the
 // device stages of two batches never overlap.
-#include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cerrno>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
 #include <mutex>
 #include <new>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "cdc_hostmem.h"
-#include "cdc_internal.h"
-#include "cdc_locator.h"
-#include "cdc_stored.h"
+#include "cdc_reader.h"
 #include "sync_plan.h"
 #include "transcode_plan.h"
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-static double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
-
-template <class F>
-static void parallel_for(int threads, size_t n, F fn)
-{
-    const size_t t = std::min<size_t>(size_t(std::max(threads, 1)), n);
-    if (t <= 1) {
-        for (size_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t k = 1; k < t; ++k) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
+using cdc::Clock;
+using cdc::parallel_for;
+using cdc::since;
 
 static int random_bytes(uint8_t *p, size_t n)
 {
@@ -84,12 +59,7 @@ static int random_bytes(uint8_t *p, size_t n)
 
 static bool compress_ok(int c) { return c == CDC_COMPRESS_NONE || c == CDC_COMPRESS_LZ4 || c == CDC_COMPRESS_GZIP; }
 
-struct InSlot {   // reader -> device stage
-    cdc::PinBuf h;
-    cdc::DevBuf d;
-    std::vector<uint64_t> eoff, elen;  // the batch's stored blobs in the arena
-    std::vector<int32_t> pre;          // a blob that could not be read (CDC_E_IO)
-};
+using InSlot = cdc::Arena;  // reader -> device stage: the batch's stored blobs
 struct OutSlot {  // device stage -> packers
     cdc::DevBuf d;
     cdc::PinBuf h;
@@ -100,19 +70,16 @@ struct OutSlot {  // device stage -> packers
 }  // namespace
 
 struct cdc_sync {
-    int device = 0;
+    cdc::PackSource ps;  // device, the source's codec, the registered packfiles and their whole indexes (keep_rows), run lock
     cdc_sync_opts o{};
-    std::vector<uint8_t> skey, dkey, known;
-    cdc_codec src{}, dst{};
-    cdc::Locator loc;  // the registered packfiles and their whole indexes (keep_rows)
+    std::vector<uint8_t> dkey, known;
+    cdc_codec src{}, dst{};  // src: ps's compression and key
     hipStream_t stream[3] = {nullptr, nullptr, nullptr};  // upload, device stage, download
     InSlot in[2];
     OutSlot out[2];
     std::vector<cdc_packer *> packers;
     int dst_form = CDC_PACKFILE_PLAIN;              // cdc_sync_set_packfile_form
     std::unique_ptr<cdc::StoredCodec> dst_stored;   // the destination's stored-form codec, made by the first run that needs it
-    std::unique_ptr<cdc::StoredCodec> stored;  // made at the first stored source (cdc_sync_add_packfiles)
-    std::mutex run_mu;
 };
 
 namespace {
@@ -124,96 +91,32 @@ struct Run {
     void *ctx;
     splan::Plan plan;
     // the stages' hand-offs: counts of batches past each point
-    std::mutex mu;
-    std::condition_variable cv;
+    cdc::Handoff hand;
     int uploaded = 0, consumed = 0, transcoded = 0, packed = 0;
-    int fail = CDC_OK;
     std::mutex sink_mu;  // on_pack is serialised; `stopped`: it returned a negative status
     bool stopped = false;
     cdc::StoredCodec *stored = nullptr;  // the destination's stored form: one codec for the run, used under sink_mu
     std::vector<uint8_t> tail;           // its scratch (sink_mu)
     cdc_sync_stats st{};
 
-    const cdc_packfile_row &row(const splan::Item &it) const { return S->loc.rows[it.pack][it.row]; }
-    // Wait until `counter` reaches `want`; false when the run has failed.
-    bool wait_for(const int &counter, int want)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return counter >= want || fail != CDC_OK; });
-        return fail == CDC_OK;
-    }
-    void advance(int &counter)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            ++counter;
-        }
-        cv.notify_all();
-    }
-    void abort_run(int status)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (fail == CDC_OK) fail = status;
-        }
-        cv.notify_all();
-    }
-    bool failed()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        return fail != CDC_OK;
-    }
+    const cdc_packfile_row &row(const splan::Item &it) const { return S->ps.loc.rows[it.pack][it.row]; }
 };
 
 // ---- reader stage ---------------------------------------------------------------
 static void reader_stage(Run &X)
 {
     cdc_sync *S = X.S;
-    if (hipSetDevice(S->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(S->ps.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     for (int k = 0; k < int(X.plan.batches.size()); ++k) {
-        if (!X.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
+        if (!X.hand.wait_for(X.consumed, k - 1)) return;  // batch k - 2 has left this input slot
         const splan::Batch &B = X.plan.batches[k];
         const splan::Item *items = &X.plan.items[B.first];
         InSlot &I = S->in[k & 1];
-        const size_t nb = size_t(B.count);
-        auto t0 = Clock::now();
-        I.eoff.assign(nb, 0);
-        I.elen.assign(nb, 0);
-        I.pre.assign(nb, CDC_OK);
-        uint64_t total = 0;
-        std::unordered_map<uint32_t, int> fds;  // the packfiles this batch reads by path, open for the batch
-        for (size_t b = 0; b < nb; ++b) {
-            I.eoff[b] = total;
-            I.elen[b] = X.row(items[b]).length;
-            total += I.elen[b];
-            const cdc::Locator::Pack &P = S->loc.packs[items[b].pack];
-            if (!P.mem && !fds.count(items[b].pack)) fds[items[b].pack] = open(P.path.c_str(), O_RDONLY | O_CLOEXEC);
-        }
-        if (!I.h.reserve(total) || !I.d.reserve(total)) {
-            for (auto &f : fds)
-                if (f.second >= 0) close(f.second);
-            return X.abort_run(CDC_E_NOMEM);
-        }
-        uint8_t *const h = I.h.as<uint8_t>();
-        parallel_for(S->o.readers, nb, [&](size_t b) {
-            const cdc::Locator::Pack &P = S->loc.packs[items[b].pack];
-            const cdc_packfile_row &R = X.row(items[b]);
-            if (P.mem) {
-                if (R.length) std::memcpy(h + I.eoff[b], P.mem + R.offset, R.length);
-                return;
-            }
-            const int fd = fds.find(items[b].pack)->second;
-            if (fd < 0 || !cdc::pread_all(fd, h + I.eoff[b], R.length, R.offset)) I.pre[b] = CDC_E_IO;
-        });
-        for (auto &f : fds)
-            if (f.second >= 0) close(f.second);
-        X.st.read_s += since(t0);
-        t0 = Clock::now();
-        if (total && (hipMemcpyAsync(I.d.data(), h, total, hipMemcpyHostToDevice, S->stream[0]) != hipSuccess ||
-                      hipStreamSynchronize(S->stream[0]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
-        X.st.h2d_s += since(t0);
-        X.advance(X.uploaded);
+        I.spans.resize(size_t(B.count));
+        for (size_t b = 0; b < I.spans.size(); ++b) I.spans[b] = cdc::span_of(items[b].pack, X.row(items[b]));
+        const int st = cdc::gather(S->ps.loc, I, S->o.readers, S->stream[0], &X.st.read_s, &X.st.h2d_s, nullptr);
+        if (st != CDC_OK) return X.hand.abort_run(st);
+        X.hand.advance(X.uploaded);
     }
 }
 
@@ -242,9 +145,9 @@ static void device_stage(Run &X)
     std::vector<uint8_t> sums, rnd;
     for (int k = 0; k < int(X.plan.batches.size()); ++k) {
         auto t0 = Clock::now();
-        if (!X.wait_for(X.uploaded, k + 1)) return;
+        if (!X.hand.wait_for(X.uploaded, k + 1)) return;
         X.st.device_wait_s += since(t0);
-        if (!X.wait_for(X.packed, k - 1)) return;  // batch k - 2 has left this output slot
+        if (!X.hand.wait_for(X.packed, k - 1)) return;  // batch k - 2 has left this output slot
         const splan::Batch &B = X.plan.batches[k];
         const splan::Item *items = &X.plan.items[B.first];
         InSlot &I = S->in[k & 1];
@@ -271,21 +174,21 @@ static void device_stage(Run &X)
         if (S->dst.key) {
             rnd.resize(size_t(m) * 56 + 1);
             const int st = random_bytes(rnd.data(), size_t(m) * 56);
-            if (st != CDC_OK) return X.abort_run(st);
+            if (st != CDC_OK) return X.hand.abort_run(st);
         }
         if (m) {
-            if (!O.d.reserve(first_cap(S, len.data(), m))) return X.abort_run(CDC_E_NOMEM);
+            if (!O.d.reserve(first_cap(S, len.data(), m))) return X.hand.abort_run(CDC_E_NOMEM);
             for (;;) {
                 const uint64_t cap = O.d.cap();
-                const int st = cdc_transcode_device_level(S->device, I.d.data(), off.data(), len.data(), m, &S->src, &S->dst,
+                const int st = cdc_transcode_device_level(S->ps.device, I.d.data(), off.data(), len.data(), m, &S->src, &S->dst,
                                                           S->o.verify ? sums.data() : nullptr,
                                                           S->dst.key ? rnd.data() : nullptr, O.d.as<uint8_t>(), cap,
                                                           oo.data(), bst.data(), S->o.level, S->stream[1]);
                 if (st == CDC_E_NOSPACE && oo[m] > cap) {
-                    if (!O.d.reserve(oo[m])) return X.abort_run(CDC_E_NOMEM);
+                    if (!O.d.reserve(oo[m])) return X.hand.abort_run(CDC_E_NOMEM);
                     continue;
                 }
-                if (st != CDC_OK) return X.abort_run(st == CDC_E_NOSPACE ? CDC_E_DEVICE : st);
+                if (st != CDC_OK) return X.hand.abort_run(st == CDC_E_NOSPACE ? CDC_E_DEVICE : st);
                 break;
             }
         }
@@ -303,8 +206,8 @@ static void device_stage(Run &X)
                 X.st.bytes_out += O.off[b + 1] - O.off[b];
         }
         ++X.st.batches;
-        X.advance(X.consumed);
-        X.advance(X.transcoded);
+        X.hand.advance(X.consumed);
+        X.hand.advance(X.transcoded);
     }
 }
 
@@ -331,28 +234,28 @@ static void sink(Run &X, cdc_packer *p)
         }
     }
     cdc_packer_reset(p);
-    if (st < 0) X.abort_run(st);
+    if (st < 0) X.hand.abort_run(st);
 }
 
 static void packer_stage(Run &X)
 {
     cdc_sync *S = X.S;
-    if (hipSetDevice(S->device) != hipSuccess) return X.abort_run(CDC_E_DEVICE);
+    if (hipSetDevice(S->ps.device) != hipSuccess) return X.hand.abort_run(CDC_E_DEVICE);
     const uint32_t np = uint32_t(S->packers.size());
     std::vector<uint32_t> bounds;
     for (int k = 0; k < int(X.plan.batches.size()); ++k) {
-        if (!X.wait_for(X.transcoded, k + 1)) return;
+        if (!X.hand.wait_for(X.transcoded, k + 1)) return;
         const splan::Batch &B = X.plan.batches[k];
         const splan::Item *items = &X.plan.items[B.first];
         OutSlot &O = S->out[k & 1];
         const uint32_t nb = uint32_t(B.count);
         const uint64_t total = O.off[nb];
         auto t0 = Clock::now();
-        if (!O.h.reserve(total)) return X.abort_run(CDC_E_NOMEM);
+        if (!O.h.reserve(total)) return X.hand.abort_run(CDC_E_NOMEM);
         const uint8_t *const image = O.h.as<uint8_t>();
         if (total && (hipMemcpyAsync(O.h.data(), O.d.data(), total, hipMemcpyDeviceToHost, S->stream[2]) != hipSuccess ||
                       hipStreamSynchronize(S->stream[2]) != hipSuccess))
-            return X.abort_run(CDC_E_DEVICE);
+            return X.hand.abort_run(CDC_E_DEVICE);
         X.st.d2h_s += since(t0);
         if (X.on_fail) {
             t0 = Clock::now();
@@ -370,21 +273,21 @@ static void packer_stage(Run &X)
             cdc_packer *pk = S->packers[p];
             for (uint32_t b = bounds[p]; b < bounds[p + 1]; ++b) {
                 if (O.status[b] != CDC_OK) continue;
-                if (X.failed()) return;
+                if (X.hand.failed()) return;
                 const cdc_packfile_row &R = X.row(items[b]);
                 const int st = cdc_packer_add_blob(pk, R.type, R.checksum, image + O.off[b], O.off[b + 1] - O.off[b]);
-                if (st < 0) return X.abort_run(st);
+                if (st < 0) return X.hand.abort_run(st);
                 if (st == 1) sink(X, pk);  // Size() > MaxSize: packerJob flushes (snapshot/snapshot.go:71)
             }
         });
         X.st.pack_s += since(t0) - (X.st.callback_s - cb0);
-        X.advance(X.packed);
+        X.hand.advance(X.packed);
     }
     // the last, partial packfiles
     const auto t0 = Clock::now();
     const double cb0 = X.st.callback_s;
     for (cdc_packer *pk : S->packers)
-        if (cdc_packer_count(pk) && !X.failed()) sink(X, pk);
+        if (cdc_packer_count(pk) && !X.hand.failed()) sink(X, pk);
     X.st.pack_s += since(t0) - (X.st.callback_s - cb0);
 }
 
@@ -398,17 +301,17 @@ static int run_sync(cdc_sync *S, const uint8_t *wanted, uint64_t nwanted, cdc_ba
     X.on_fail = on_fail;
     X.ctx = ctx;
     std::vector<splan::Pack> packs;
-    for (const auto &rows : S->loc.rows) packs.push_back(splan::Pack{rows.data(), rows.size()});
+    for (const auto &rows : S->ps.loc.rows) packs.push_back(splan::Pack{rows.data(), rows.size()});
     splan::plan(packs.data(), packs.size(), S->known.data(), S->o.nknown, wanted, nwanted, S->o.batch_bytes, X.plan);
     X.st.skipped = X.plan.skipped;
     X.st.path = int32_t(tplan::choose_path(S->src.compress, S->src.key != nullptr, S->dst.compress, S->dst.key != nullptr));
     for (cdc_packer *pk : S->packers) cdc_packer_reset(pk);
     if (!X.plan.batches.empty()) {
-        if (hipSetDevice(S->device) != hipSuccess) return CDC_E_DEVICE;
+        if (hipSetDevice(S->ps.device) != hipSuccess) return CDC_E_DEVICE;
         if (S->dst_form == CDC_PACKFILE_STORED) {
             if (!S->dst_stored) {
                 std::unique_ptr<cdc::StoredCodec> c(new cdc::StoredCodec());
-                const int st = c->open(S->device, S->dst.compress, S->dst.key);
+                const int st = c->open(S->ps.device, S->dst.compress, S->dst.key);
                 if (st != CDC_OK) return st;
                 S->dst_stored = std::move(c);
             }
@@ -418,7 +321,7 @@ static int run_sync(cdc_sync *S, const uint8_t *wanted, uint64_t nwanted, cdc_ba
             try {
                 stage(X);
             } catch (...) {
-                X.abort_run(CDC_E_NOMEM);
+                X.hand.abort_run(CDC_E_NOMEM);
             }
         };
         std::thread reader(guarded, reader_stage);
@@ -433,7 +336,7 @@ static int run_sync(cdc_sync *S, const uint8_t *wanted, uint64_t nwanted, cdc_ba
         X.st.struct_size = uint32_t(std::min<size_t>(stats->struct_size, sizeof(X.st)));
         std::memcpy(stats, &X.st, X.st.struct_size);
     }
-    return X.fail;
+    return X.hand.fail;
 }
 
 }  // namespace
@@ -461,18 +364,17 @@ int cdc_sync_new(int device, const cdc_sync_opts *opts, cdc_sync **out)
     auto *s = new (std::nothrow) cdc_sync();
     if (!s) return CDC_E_NOMEM;
     try {
-        s->device = device;
+        s->ps.open(device, opts->src.compress, opts->src.key);
         s->o = *opts;
-        if (opts->src.key) s->skey.assign(opts->src.key, opts->src.key + 32);
         if (opts->dst.key) s->dkey.assign(opts->dst.key, opts->dst.key + 32);
         if (opts->nknown) s->known.assign(opts->known, opts->known + splan::kKeyBytes * opts->nknown);
-        s->src = cdc_codec{opts->src.compress, s->skey.empty() ? nullptr : s->skey.data()};
+        s->src = cdc_codec{s->ps.compress, s->ps.key_ptr()};
         s->dst = cdc_codec{opts->dst.compress, s->dkey.empty() ? nullptr : s->dkey.data()};
         s->o.src.key = s->o.dst.key = s->o.known = nullptr;
         if (!s->o.readers) s->o.readers = 8;
         if (!s->o.packers) s->o.packers = 8;
         if (!s->o.batch_bytes) s->o.batch_bytes = 64ull << 20;
-        s->loc.keep_rows = true;
+        s->ps.loc.keep_rows = true;
         for (int p = 0; p < s->o.packers; ++p) {
             cdc_packer *pk = nullptr;
             if (cdc_packer_new(s->o.packfile_max, &pk) != CDC_OK) throw std::bad_alloc();
@@ -494,36 +396,17 @@ int cdc_sync_new(int device, const cdc_sync_opts *opts, cdc_sync **out)
 
 int cdc_sync_add_packfile(cdc_sync *s, const uint8_t *bytes, uint64_t len)
 {
-    if (!s || (!bytes && len)) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(s->run_mu);
-    try {
-        return s->loc.add_memory(bytes, len);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return s && (bytes || !len) ? s->ps.add_memory(bytes, len) : CDC_E_INVALID;
 }
 
 int cdc_sync_add_packfile_path(cdc_sync *s, const char *path)
 {
-    if (!s || !path) return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(s->run_mu);
-    try {
-        return s->loc.add_path(path);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return s && path ? s->ps.add_path(path) : CDC_E_INVALID;
 }
 
 int cdc_sync_add_packfiles(cdc_sync *s, const cdc_packfile_src *srcs, uint32_t n, int32_t *status)
 {
-    if (!s || cdc::add_packfiles_invalid(srcs, n, status)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(s->run_mu, std::try_to_lock);
-    if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
-    try {
-        return cdc::add_packfiles(s->loc, s->stored, s->device, s->src.compress, s->src.key, srcs, n, status);
-    } catch (...) {
-        return CDC_E_NOMEM;
-    }
+    return s ? s->ps.add_many(srcs, n, status) : CDC_E_INVALID;
 }
 
 int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backup_pack_fn on_pack, cdc_sync_blob_fn on_fail,
@@ -531,7 +414,7 @@ int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backu
 {
     if (!s || !on_pack || (stats && stats->struct_size < 8) || (wanted && !splan::sorted33(wanted, nwanted)))
         return CDC_E_INVALID;
-    std::lock_guard<std::mutex> lk(s->run_mu);
+    std::lock_guard<std::mutex> lk(s->ps.run_mu);
     try {
         return run_sync(s, wanted, nwanted, on_pack, on_fail, ctx, stats);
     } catch (const std::bad_alloc &) {
@@ -542,7 +425,7 @@ int cdc_sync_run(cdc_sync *s, const uint8_t *wanted, uint64_t nwanted, cdc_backu
 int cdc_sync_set_packfile_form(cdc_sync *s, int form)
 {
     if (!s || (form != CDC_PACKFILE_PLAIN && form != CDC_PACKFILE_STORED)) return CDC_E_INVALID;
-    std::unique_lock<std::mutex> lk(s->run_mu, std::try_to_lock);
+    std::unique_lock<std::mutex> lk(s->ps.run_mu, std::try_to_lock);
     if (!lk.owns_lock()) return CDC_E_INVALID;  // a run is in progress
     s->dst_form = form;
     return CDC_OK;
@@ -551,18 +434,8 @@ int cdc_sync_set_packfile_form(cdc_sync *s, int form)
 void cdc_sync_free(cdc_sync *s)
 {
     if (!s) return;
-    bool any = false;
-    for (auto &st : s->stream) any = any || st;
-    if (any) {
-        (void)hipSetDevice(s->device);
-        for (auto &st : s->stream)
-            if (st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-    }
+    s->ps.release(s->stream, 3);
     for (cdc_packer *pk : s->packers) cdc_packer_free(pk);
-    if (!s->skey.empty()) std::memset(s->skey.data(), 0, s->skey.size());
     if (!s->dkey.empty()) std::memset(s->dkey.data(), 0, s->dkey.size());
     delete s;  // the slots' buffers go with it, the streams drained above
 }

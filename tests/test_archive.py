@@ -15,6 +15,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import pack_loss  # noqa: E402
 from datagen import low_entropy, random_bytes  # noqa: E402
 from plakar_amd import _lib, archive, restore, snapshot  # noqa: E402
 from plakar_amd.archive import ArchiveEntry  # noqa: E402
@@ -238,3 +239,65 @@ def test_a_damaged_blob_ends_the_run_and_leaves_no_file(backups, tmp_path, key, 
     good = archive.archive_files(ents, packs, key=key, compression=compression, format=fmt, batch_bytes=64 << 10)[0]
     assert len(b"".join(pieces)) < len(good), "nothing more is written after the failure"
     assert good.startswith(b"".join(pieces))
+
+
+def _three(objs, hurt=None):
+    return [ArchiveEntry("ok", objs[3], mtime=1), ArchiveEntry("hurt", hurt or objs[5], mtime=2), ArchiveEntry("after", objs[4])]
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+@pytest.mark.parametrize("fmt", ["tar", "tarball"])
+def test_an_unreadable_packfile_ends_the_run_and_names_the_entry(backups, tmp_path, fmt, how):
+    """Registered by path, then lost before the run: CDC_E_IO, the first entry
+    with a blob in the lost bytes named, no file left."""
+    objs, packs = backups(KEY, "LZ4")
+    ents = _three(objs)
+    paths = pack_loss.write_packs(tmp_path, packs)
+    path = str(tmp_path / "out")
+    with archive.ArchiveSession(key=KEY, format=fmt, writers=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        used = [e.obj for e in ents]
+        lost = pack_loss.lose(paths, packs, pack_loss.first_home(packs)[bytes(objs[5].Chunks[0].Checksum)][0], how, used)
+        want = next(i for i, o in enumerate(used) if pack_loss.first_lost(o, lost) is not None)
+        with pytest.raises(_lib.CdcError) as e:
+            s.run(ents, path=path)
+    assert e.value.status == _lib.CDC_E_IO and e.value.entry == want
+    assert not os.path.exists(path)
+
+
+@pytest.mark.parametrize("key,compression", CONFIGS, ids=["plain", "lz4-sealed"])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["short", "long"])
+@pytest.mark.parametrize("fmt", ["tar", "tarball"])
+def test_a_wrong_recorded_length_ends_the_run_and_names_the_entry(backups, tmp_path, fmt, delta, key, compression):
+    objs, packs = backups(key, compression)
+    chunks5 = [(bytes(c.Checksum), c.Length) for c in objs[5].Chunks]
+    (c0, n0) = chunks5[0]
+    ents = _three(objs, _obj([(c0, n0 + delta)] + chunks5[1:]))
+    path = str(tmp_path / "out")
+    with pytest.raises(_lib.CdcError) as e:
+        archive.archive_files(ents, packs, path=path, key=key, compression=compression, format=fmt)
+    assert e.value.status == _lib.CDC_E_MISMATCH and e.value.entry == 1
+    assert not os.path.exists(path)
+    good, statuses, st = archive.archive_files(_three(objs), packs, key=key, compression=compression, format=fmt)
+    assert statuses == [0, 0, 0] and st["batches"] == 1, "the three entries are one batch"
+
+
+@pytest.mark.parametrize("key,compression", CONFIGS, ids=["plain", "lz4-sealed"])
+def test_two_wrong_lengths_in_one_batch_name_the_first_entry(backups, key, compression):
+    """One blob decodes shorter than its recorded Length, a later one longer
+    (by more, so the batch overflows its plaintext room and is decoded one by
+    one): the run names the first wrong entry, as it does when nothing
+    overflows."""
+    objs, packs = backups(key, compression)
+    bad = []
+    for i, delta in ((5, 1), (2, -2)):
+        chunks = [(bytes(c.Checksum), c.Length) for c in objs[i].Chunks]
+        (c0, n0) = chunks[0]
+        bad.append(_obj([(c0, n0 + delta)] + chunks[1:]))
+    ents = [ArchiveEntry("ok", objs[3], mtime=1), ArchiveEntry("short", bad[0], mtime=2),
+            ArchiveEntry("long", bad[1], mtime=3), ArchiveEntry("after", objs[4])]
+    for order in (ents, [ents[0], ents[2], ents[1], ents[3]]):
+        with pytest.raises(_lib.CdcError) as e:
+            archive.archive_files(order, packs, key=key, compression=compression, format="tar")
+        assert e.value.status == _lib.CDC_E_MISMATCH and e.value.entry == 1

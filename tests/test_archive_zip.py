@@ -21,6 +21,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import pack_loss  # noqa: E402
 from datagen import low_entropy, random_bytes, text_like  # noqa: E402
 from plakar_amd import _lib, archive, encode, restore, snapshot  # noqa: E402
 from plakar_amd.archive import ArchiveEntry  # noqa: E402
@@ -444,3 +445,43 @@ def test_an_archive_without_files_is_the_end_record(backups):
         data, statuses, st = archive.zip_files(ents, packs, key=None, compression=None)
         assert data == END_RECORD and statuses == [0] * len(ents) and st["entries"] == 0 and st["batches"] == 0
         assert zipfile.ZipFile(io.BytesIO(data)).namelist() == []
+
+
+def _three(objs, hurt=None):
+    return [ArchiveEntry("ok", objs[3], mtime=1), ArchiveEntry("hurt", hurt or objs[5], mtime=2), ArchiveEntry("after", objs[4])]
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+def test_an_unreadable_packfile_ends_the_run_and_names_the_entry(backups, tmp_path, how):
+    """Registered by path, then lost before the run: CDC_E_IO, the first entry
+    with a blob in the lost bytes named, no file left."""
+    objs, packs = backups(KEY, "LZ4")
+    ents = _three(objs)
+    paths = pack_loss.write_packs(tmp_path, packs)
+    path = str(tmp_path / "out.zip")
+    with archive.ZipSession(key=KEY, writers=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        used = [e.obj for e in ents]
+        lost = pack_loss.lose(paths, packs, pack_loss.first_home(packs)[bytes(objs[5].Chunks[0].Checksum)][0], how, used)
+        want = next(i for i, o in enumerate(used) if pack_loss.first_lost(o, lost) is not None)
+        with pytest.raises(_lib.CdcError) as e:
+            s.run(ents, path=path)
+    assert e.value.status == _lib.CDC_E_IO and e.value.entry == want
+    assert not os.path.exists(path)
+
+
+@pytest.mark.parametrize("key,compression", CONFIGS[:2], ids=IDS[:2])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["short", "long"])
+def test_a_wrong_recorded_length_ends_the_run_and_names_the_entry(backups, tmp_path, delta, key, compression):
+    objs, packs = backups(key, compression)
+    chunks5 = [(bytes(c.Checksum), c.Length) for c in objs[5].Chunks]
+    (c0, n0) = chunks5[0]
+    ents = _three(objs, _obj([(c0, n0 + delta)] + chunks5[1:]))
+    path = str(tmp_path / "out.zip")
+    with pytest.raises(_lib.CdcError) as e:
+        archive.zip_files(ents, packs, path=path, key=key, compression=compression)
+    assert e.value.status == _lib.CDC_E_MISMATCH and e.value.entry == 1
+    assert not os.path.exists(path)
+    good, statuses, st = archive.zip_files(_three(objs), packs, key=key, compression=compression)
+    assert statuses == [0, 0, 0] and st["batches"] == 1, "the three entries are one batch"

@@ -11,6 +11,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import pack_loss  # noqa: E402
 from datagen import low_entropy, random_bytes  # noqa: E402
 from plakar_amd import _lib, check, restore, snapshot  # noqa: E402
 
@@ -410,3 +411,25 @@ def test_packfiles_by_path_and_from_memory_and_a_reused_session(corpus, backups,
     assert "device_bytes" in counters and "seam_bytes" in counters
     for k in counters:
         assert stats_path[k] == stats_mem[k] == stats_again[k], k
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+def test_an_unreadable_packfile_fails_exactly_its_files(corpus, backups, tmp_path, how):
+    """Registered by path, then lost before the run: CDC_E_IO and the first
+    lost chunk for the files with a blob there, every other file checked."""
+    _, files = corpus
+    objs, packs = backups(KEY, "LZ4")
+    paths = pack_loss.write_packs(tmp_path, packs)
+    with check.CheckSession(key=KEY, batch_bytes=8 << 20, threads=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        lost = pack_loss.lose(paths, packs, pack_loss.pick(objs, packs), how, objs)
+        res, st = s.run(objs)
+    want = [pack_loss.first_lost(o, lost) for o in objs]
+    assert any(w is not None for w in want) and any(w is None and f for w, f in zip(want, files))
+    for i, (r, f, w) in enumerate(zip(res, files, want)):
+        if w is None:
+            assert r["status"] == 0 and r["bad_chunk"] == -1 and r["checksum"] == _sha(f), (i, r)
+        else:
+            assert (r["status"], r["bad_chunk"], r["hashed"], r["checksum"]) == (_lib.CDC_E_IO, w, 0, None), (i, r)
+    assert st["failed_files"] == sum(w is not None for w in want)

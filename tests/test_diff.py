@@ -9,6 +9,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import diff_ref  # noqa: E402
+import pack_loss  # noqa: E402
 from datagen import random_bytes  # noqa: E402
 from plakar_amd import _lib, restore, snapshot  # noqa: E402
 from plakar_amd.chunking import Configuration  # noqa: E402
@@ -292,3 +293,56 @@ def test_reused_session_and_packfiles_by_path(corpus, backups, expected, tmp_pat
         r, _ = s.run(jobs[:1])
         name, a, b = pairs[0]
         assert r[0]["text"] == diff_ref.expected_diff(a, b, b"old/" + name.encode(), b"new/" + name.encode(), n=1)
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+def test_an_unreadable_packfile_fails_exactly_its_pairs(corpus, backups, expected, tmp_path, how):
+    """Registered by path, then lost before the run: CDC_E_IO with the side and
+    the first lost chunk (a's before b's) for the pairs with a blob there, the
+    text of every other pair."""
+    _, pairs = corpus
+    objs, packs = backups(KEY, "LZ4")
+    jobs = _jobs(objs, pairs)
+    paths = pack_loss.write_packs(tmp_path, packs)
+    with snapshot.DiffSession(KEY, "LZ4", threads=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        lost = pack_loss.lose(paths, packs, pack_loss.pick(objs, packs), how, objs)
+        res, st = s.run(jobs)
+    want = []
+    for a, b, _, _ in jobs:
+        la, lb = pack_loss.first_lost(a, lost), pack_loss.first_lost(b, lost)
+        want.append((0, la) if la is not None else (1, lb) if lb is not None else None)
+    assert any(w is not None for w in want) and any(w is None for w in want)
+    for k, (r, w) in enumerate(zip(res, want)):
+        if w is None:
+            assert r["status"] == 0 and r["text"] == expected[k], k
+        else:
+            assert (r["status"], r["bad_side"], r["bad_chunk"], r["text"]) == (_lib.CDC_E_IO, w[0], w[1], b""), (k, r["status"])
+    assert st["failed_pairs"] == sum(w is not None for w in want) and st["batches"] == 1
+
+
+@pytest.mark.parametrize("key,compression", [(KEY, "LZ4"), (None, None)])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["short", "long"])
+def test_a_wrong_recorded_length_fails_its_pair_alone(corpus, backups, expected, key, compression, delta):
+    """The first chunk's recorded Length one byte off, on side a and on side b:
+    that pair is CDC_E_MISMATCH at that side's chunk 0, the pairs of the same
+    batch get their text."""
+    _, pairs = corpus
+    objs, packs = backups(key, compression)
+    jobs = _jobs(objs, pairs)
+    i = [n for n, _, _ in pairs].index("binary")
+    bad = []
+    for side in (0, 1):
+        chunks = [(bytes(c.Checksum), c.Length) for c in objs[2 * i + side].Chunks]
+        assert len(chunks) >= 2
+        (c0, n0) = chunks[0]
+        bad.append(_obj([(c0, n0 + delta)] + chunks[1:]))
+    more = [(bad[0], objs[2 * i + 1], "a", "b"), (objs[2 * i], bad[1], "a", "b")]
+    res, st = snapshot.diff_files(jobs + more, packs, key=key, compression=compression)
+    n = len(jobs)
+    assert [r["status"] for r in res[:n]] == [0] * n and [r["text"] for r in res[:n]] == expected
+    for side in (0, 1):
+        r = res[n + side]
+        assert (r["status"], r["bad_side"], r["bad_chunk"], r["text"]) == (_lib.CDC_E_MISMATCH, side, 0, b""), side
+    assert st["failed_pairs"] == 2 and st["batches"] == 1

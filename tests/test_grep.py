@@ -10,6 +10,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import grep_ref as gref  # noqa: E402
+import pack_loss  # noqa: E402
 from datagen import random_bytes  # noqa: E402
 from plakar_amd import _lib, grep, restore, snapshot  # noqa: E402
 from plakar_amd.chunking import Configuration  # noqa: E402
@@ -259,3 +260,44 @@ def test_stored_packfiles_and_rows_give_the_same_hits(corpus, backups, judged, k
         res, _ = s.run(objs, PATTERNS)
     for i, (f, r) in enumerate(zip(files, res)):
         _holds(r, judged[False][i], len(f), what=i)
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+def test_an_unreadable_packfile_fails_exactly_its_files(corpus, backups, judged, tmp_path, how):
+    """Registered by path, then lost before the run: CDC_E_IO and the first
+    lost chunk for the files with a blob there, every other file searched."""
+    _, files = corpus
+    objs, packs = backups(KEY, "LZ4")
+    paths = pack_loss.write_packs(tmp_path, packs)
+    with snapshot.GrepSession(KEY, "LZ4", threads=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        lost = pack_loss.lose(paths, packs, pack_loss.pick(objs, packs), how, objs)
+        res, st = s.run(objs, PATTERNS)
+    want = [pack_loss.first_lost(o, lost) for o in objs]
+    assert any(w is not None for w in want) and any(w is None and f for w, f in zip(want, files))
+    for i, (f, r, w) in enumerate(zip(files, res, want)):
+        if w is None:
+            _holds(r, judged[False][i], len(f), what=i)
+        else:
+            assert (r["status"], r["bad_chunk"], r["matched"], len(r["hits"])) == (_lib.CDC_E_IO, w, 0, 0), i
+    assert st["failed_files"] == sum(w is not None for w in want) and st["batches"] == 1
+
+
+@pytest.mark.parametrize("key,compression", [(KEY, "LZ4"), (None, None)])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["short", "long"])
+def test_a_wrong_recorded_length_fails_its_file_alone(corpus, backups, judged, key, compression, delta):
+    """The first chunk's recorded Length one byte off: that file is
+    CDC_E_MISMATCH at chunk 0, the files of the same batch are searched."""
+    _, files = corpus
+    objs, packs = backups(key, compression)
+    chunks = [(bytes(c.Checksum), c.Length) for c in objs[STRADDLE].Chunks]
+    assert len(chunks) >= 2
+    (c0, n0) = chunks[0]
+    res, st = snapshot.grep_files(list(objs) + [_obj([(c0, n0 + delta)] + chunks[1:])], packs, PATTERNS, key=key,
+                                  compression=compression)
+    n = len(files)
+    for i, (f, r) in enumerate(zip(files, res[:n])):
+        _holds(r, judged[False][i], len(f), what=i)
+    assert (res[n]["status"], res[n]["bad_chunk"], res[n]["matched"], len(res[n]["hits"])) == (_lib.CDC_E_MISMATCH, 0, 0, 0)
+    assert st["failed_files"] == 1 and st["batches"] == 1

@@ -3,12 +3,14 @@ restore.SnapshotFile): every range against a slice of the source file, the
 work counters against the chunk lists, per-range failures, and the file object
 with VFilep's rules."""
 import io
+import types
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import pack_loss  # noqa: E402
 from datagen import low_entropy, random_bytes  # noqa: E402
 from plakar_amd import _lib, restore, snapshot  # noqa: E402
 from plakar_amd.chunking import Configuration  # noqa: E402
@@ -261,3 +263,44 @@ def test_snapshot_file(corpus, backups, key, compression):
         f.close()
         with pytest.raises(ValueError):
             f.read(1)
+
+
+@pytest.mark.parametrize("how", ["removed", "truncated"])
+def test_an_unreadable_packfile_fails_exactly_the_ranges_that_touch_it(corpus, backups, tmp_path, how):
+    """Registered by path, then lost before the run: CDC_E_IO for the ranges
+    that touch a blob in the lost bytes, every other range's bytes."""
+    _, files = corpus
+    objs, packs = backups(KEY, "LZ4")
+    paths = pack_loss.write_packs(tmp_path, packs)
+    ranges = _ranges(objs)
+    with restore.RestoreSession(key=KEY, writers=3) as s:
+        for q in paths:
+            s.add_packfile(q)
+        k = pack_loss.first_home(packs)[bytes(objs[3].Chunks[len(objs[3].Chunks) // 2].Checksum)][0]
+        lost = pack_loss.lose(paths, packs, k, how, objs)
+        contents, statuses, st = s.read_ranges(objs, ranges)
+    want = [_lib.CDC_E_IO if _touch(objs, r, lost) else 0 for r in ranges]
+    assert statuses == want and 0 in want and _lib.CDC_E_IO in want
+    for (fi, off, ln), got, w in zip(ranges, contents, want):
+        assert got == (None if w else files[fi][off:off + ln])
+    assert st["failed_ranges"] == sum(1 for w in want if w)
+
+
+@pytest.mark.parametrize("key,compression", [REPOS[0], REPOS[2]], ids=[IDS[0], IDS[2]])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["short", "long"])
+def test_a_wrong_recorded_length_fails_its_ranges_alone(corpus, backups, key, compression, delta):
+    """The first chunk's recorded Length one byte off and a range over that
+    whole chunk, so the blob is decoded whole: CDC_E_MISMATCH for that range,
+    the ranges of the same batch get their bytes."""
+    _, files = corpus
+    objs, packs = backups(key, compression)
+    chunks = [(bytes(c.Checksum), c.Length) for c in objs[4].Chunks]
+    (c0, n0) = chunks[0]
+    bad = types.SimpleNamespace(Chunks=[types.SimpleNamespace(Checksum=c, Length=n) for c, n in [(c0, n0 + delta)] + chunks[1:]])
+    n = len(objs)
+    ranges = [(3, 10, 100_000), (n, 0, n0 + delta + 10), (4, 0, n0 + 10), (n, n0 + delta, 5), (6, 1000, 5)]
+    contents, statuses, st = snapshot.read_ranges(list(objs) + [bad], ranges, packs, key=key, compression=compression)
+    M = _lib.CDC_E_MISMATCH
+    assert statuses == [0, M, 0, 0, 0] and st["failed_ranges"] == 1 and st["batches"] == 1
+    assert contents[0] == files[3][10:100_010] and contents[1] is None and contents[2] == files[4][:n0 + 10]
+    assert contents[3] == files[4][n0:n0 + 5] and contents[4] == files[6][1000:1005]
